@@ -10,12 +10,17 @@ algorithm/algorithm.inc:1491-1720); whole solves run back to back and an iterati
 (chase_hip_solver_set_iteration_hook) marks the iteration boundaries: W warm-up iterations are skipped, then EXACTLY K
 iterations are timed between two (device sync + barrier) brackets.  Everything a solve does before its first filter
 (start vectors, first QR, Lanczos bounds) belongs to that solve's first iteration.  A complete solve takes 9 iterations.
+On one GPU the solve in flight ends with the last warm-up step, the timed steps start with a fresh solve, and the solve
+in flight ends with the last timed step.
   metric  = Chebyshev-filter HEMM GFLOP/s = flops of the reference's model (2*F*N^2 per filtered vector, F = 4 complex:
             algorithm/performance.hpp:248-260) of the filter HEMMs of the timed iterations / HIP-event time between
             FilterPhaseStart/End (max over ranks, all-reduces included), whole job
-  extra   = eigenpairs_per_sec (nev / wall of the complete solves), per-phase seconds, roofline (EXECUTED MFMA flops:
-            the complex filter kernel forms a complex product from 3 real MFMA products), the four-product kernel timed
-            on full-width HEMMs, the CPU oracle on the host cores.
+  extra   = roofline of the timed filter HEMMs (EXECUTED MFMA flops: the complex filter kernel forms a complex product
+            from 3 real MFMA products); with --full also eigenpairs_per_sec (nev / wall of the complete solves), per-phase
+            seconds, the parity guard on a complete solve, the four-product kernel timed on full-width HEMMs, the CPU
+            oracle on the host cores.
+`--dump-outputs DIR` (one GPU) writes the Ritz values, residuals and a seeded row sample of the Ritz vectors as they
+stand after the last timed step to DIR/*.npy: the inputs are seeded, so two builds can be compared output for output.
 `python bench.py --gpus N` with N > 1 starts its N ranks itself (one process per GPU, RCCL row/column all-reduces over
 xGMI on the reference's 2D grid, grid/mpiGrid2D.hpp); under torch.distributed.run (RANK set) it is one of the ranks.
 `--ranks threads` runs the N ranks as threads of ONE process (one thread per GPU).  A multi-GPU run proves its transport
@@ -239,8 +244,11 @@ class StepTimer:
     sync(): device synchronisation of this rank; barrier(): all ranks; snapshot(): dict of cumulative counters.  The
     boundaries are bracketed sync -> barrier -> clock on both sides, like the contract asks for whole steps."""
 
-    def __init__(self, steps, warmup, sync, barrier, snapshot, progress=None, before_timed=None):
+    def __init__(self, steps, warmup, sync, barrier, snapshot, progress=None, before_timed=None, cut=False):
         self.steps, self.warmup = steps, warmup
+        # cut: the solve in flight at the end of the warm-up is ended there and the timed steps start with a fresh solve,
+        # and the solve in flight at the end of the timed steps is ended there too (nothing runs after the last timed step)
+        self.cut = cut
         self.sync, self.barrier, self.snapshot = sync, barrier, snapshot
         self.before_timed = before_timed      # called once, right before the opening bracket of the timed region
         self.boundary = 0                     # outer iterations completed so far (all solves)
@@ -299,6 +307,13 @@ class StepTimer:
                 self.t1, self.c1 = self._bracket()
                 if self.in_solve:
                     self.outside[self.solve_index] = self.outside.get(self.solve_index, 0.0) + (self.t1 - drained)
+                if self.cut:
+                    return True                # end the solve at the last timed step
+        if self.cut:
+            # the warm-up's solve ends at the last warm-up step; run_timed_solves opens the timed region before the next
+            # solve, so the timed steps are the first iterations of fresh solves (the costliest ones of a solve: W warm-up
+            # steps then cost about what W timed steps do)
+            return self.t0 is None and self.boundary == self.warmup
         self.start_if_due()
         # never cut a solve short: the solve in flight when the timed region ends runs to completion (its remaining
         # iterations are the cheap ones), so that the LAST solve is always a complete one and the independent residual
@@ -309,9 +324,12 @@ class StepTimer:
         return self.c1[key] - self.c0[key]
 
 
-def run_timed_solves(s, timer, nev, capture):
+def run_timed_solves(s, timer, nev, capture, after_timed=None, need_complete=True):
     """Back-to-back solves until the timer has its iterations.  capture() returns (eigenvalues, residuals) of the solver's
-    last solve; the last COMPLETE solve (all nev pairs locked) is what the parity guard checks."""
+    last solve; the last COMPLETE solve (all nev pairs locked) is what the parity guard checks.  after_timed() is called
+    once, right after the solve that holds the last timed step has returned.  With a cutting timer (StepTimer(cut=True))
+    and need_complete, a timed region that ends inside a solve is followed by one complete, untimed solve, so that the
+    last solve is a complete one; without need_complete nothing runs after the timed region."""
     complete, last_complete = [], None
     s.set_iteration_hook(timer.hook)
     timer.start_if_due()
@@ -332,7 +350,14 @@ def run_timed_solves(s, timer, nev, capture):
             complete.append(st)
             last_complete = capture()
         timer.solve_index += 1
-        if timer.done and timer.complete_solves >= 1:
+        if timer.done and after_timed is not None:
+            after_timed()
+            after_timed = None
+        if timer.cut:
+            if timer.done and (not need_complete or st["locked"] >= nev):
+                break
+            timer.start_if_due()               # (the timed region opens between two solves)
+        elif timer.done and timer.complete_solves >= 1:
             break
         if timer.solve_index > timer.warmup + timer.steps + 2:
             raise RuntimeError("bench: solves do not converge (no complete solve within the iteration budget)")
@@ -431,13 +456,35 @@ def attach_replay(out, workload):
         pass
 
 
+DUMP_ROWS = 1024                 # --dump-outputs: rows of the eigenvector block written (a fixed, seeded sample)
+
+
+def dump_outputs(path, N, nev, ritzv, resid, V):
+    """--dump-outputs: what a caller of the solve receives after the last timed step - the Ritz values and residuals of all
+    nev + nex columns and the first nev Ritz vectors on a fixed, seeded sample of DUMP_ROWS rows (real and imaginary part
+    in the last axis for a complex workload), all float64 (< 64 MB for every workload)."""
+    os.makedirs(path, exist_ok=True)
+    rows = np.sort(np.random.default_rng(20240).choice(N, size=min(N, DUMP_ROWS), replace=False))
+    vs = np.asarray(V)[rows, :nev]
+    if np.iscomplexobj(vs):
+        vs = np.stack([vs.real, vs.imag], axis=-1)
+    arrays = {"ritz_values": ritzv, "residuals": resid, "ritz_vectors_sample": vs, "ritz_vectors_sample_rows": rows}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def run_single(args):
+    """One GPU, the single-GPU Impl.  A plain run sets up, runs W warm-up and K timed outer iterations (StepTimer(cut=True):
+    the timed steps start with a fresh solve and nothing runs after the last of them) and reports the filter rate of the
+    timed steps.  --full adds what takes runs or checks of its own: the CPU baseline child, one complete solve behind the
+    timed steps for the parity guard (analytic spectrum, residuals recomputed from H), the full-width 4M / 3M kernel probes,
+    the bare MFMA loop and the figures recorded in profiles/."""
     from chase_amd.capi import Context, Solver, gemm_counters
     N, cplx, nev, nex = WORKLOADS[args.workload]
     if args.n:
         N = args.n
     nevex = nev + nex
-    cpu_job = None if args.no_cpu_baseline else CpuBaselineJob(N, cplx, nevex, args.cpu_budget)
+    cpu_job = None if (args.no_cpu_baseline or not args.full) else CpuBaselineJob(N, cplx, nevex, args.cpu_budget)
     ctx = Context(0)
     info = ctx.info()
     dH = ctx.gen_clement(N, cplx, scale=MATRIX_SCALE / N, perturb=MATRIX_PERTURB, seed=42)
@@ -451,9 +498,14 @@ def run_single(args):
         return {"filter_ms": s.get("filter_ms"), "hemm_calls": s.get("hemm_calls"),
                 "reused": s.get("hemm_reused_vecs"), "model": model, "exec": execd, "gemms": calls}
 
+    def after_timed():
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, N, nev, s.ritzv, s.resid(), s.V)
+
     timer = StepTimer(args.steps, args.warmup, ctx.sync, lambda: None, snapshot,
-                      before_timed=(cpu_job.join if cpu_job is not None else None))
-    complete, last = run_timed_solves(s, timer, nev, lambda: (s.ritzv[:nev].copy(), s.resid()[:nev].copy()))
+                      before_timed=(cpu_job.join if cpu_job is not None else None), cut=True)
+    complete, last = run_timed_solves(s, timer, nev, lambda: (s.ritzv[:nev].copy(), s.resid()[:nev].copy()),
+                                      after_timed=after_timed, need_complete=args.full)
     wall = timer.t1 - timer.t0
     filt_s = timer.diff("filter_ms") * 1e-3
     calls = int(timer.diff("hemm_calls"))
@@ -464,15 +516,6 @@ def run_single(args):
     formula = 2.0 * F * N * N * hemm_vecs
     assert abs(model_flops - formula) <= 1e-9 * formula, (model_flops, formula)
     gflops = model_flops / filt_s / 1e9
-    lam, resid = last
-    spec = spectrum_check(lam, N, nev)
-    # independent check outside the timed region (the reference's solve tests: tests/chase_serial_solve.cpp:144-148,195-199):
-    # one fresh four-product H V over the nev eigenvectors of the last solve + the residual-norm kernel.  The solver's own
-    # residuals come from (H Q) A left behind by Rayleigh-Ritz, these from H itself.
-    resid_re = s.recompute_residuals(nev, lam)
-    ok = converged_ok(lam, resid, resid_re, s.get("tol"), spec)
-    st = complete[-1]
-    solve_s = float(np.mean([c["t_all"] for c in complete]))
     out = {
         "metric": "chebyshev_filter_hemm_gflops", "value": gflops, "unit": "GFLOP/s",
         "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": wall / args.steps * 1e3,
@@ -480,34 +523,47 @@ def run_single(args):
         "dtype": "complex f64" if cplx else "f64", "data": "synthetic",
         "config": {"workload": f"{args.workload}: ChASE solve, perturbed Clement-type Hermitian (x100/N) N={N} "
                                f"{'complex' if cplx else 'real'} fp64, nev={nev} nex={nex}, tol 1e-10, deg 20 opt, 1x1 grid; "
-                               "step = one outer iteration (filter+QR+RR+residuals+locking), solves back to back",
+                               "step = one outer iteration (filter+QR+RR+residuals+locking), solves back to back, "
+                               "the timed steps from a fresh solve",
                    "N": N, "nev": nev, "nex": nex, "grid": "1x1", "step": "outer iteration"},
-        "eigenpairs_per_sec": nev / solve_s, "solve_seconds": solve_s, "complete_solves": len(complete),
+        "full": bool(args.full), "complete_solves": len(complete),
         "pct_fp64_mfma_peak": 100.0 * exec_flops / filt_s / 1e12 / FP64_MFMA_PEAK_TFLOPS,
-        "converged": ok, "max_resid": float(np.max(resid)), "max_resid_recomputed": float(np.max(resid_re)),
-        "residuals_rechecked_on_the_tolerance": int(s.get("resd_rechecked")),
-        "spectrum_check": spec,
-        "iterations_per_solve": st["iterations"], "filtered_vecs_per_solve": st["filtered_vecs"],
         "timed": {"filtered_vecs": timer.filtered_timed, "hemm_vecs": hemm_vecs, "first_step_vecs_from_rr": reused,
                   "filter_seconds_device": filt_s, "wall_seconds": wall,
                   "iterations": [{"solve": a, "iteration": b, "filtered_vecs": c, "seconds": d} for a, b, c, d in timer.per_iter]},
-        "phase_seconds_last_complete_solve": {k: st[k] for k in PHASES},
         "device": info["name"],
         "roofline": roofline_object(model_flops, exec_flops, filt_s, calls, 1),
     }
+    if complete:
+        st = complete[-1]
+        solve_s = float(np.mean([c["t_all"] for c in complete]))
+        out.update({"eigenpairs_per_sec": nev / solve_s, "solve_seconds": solve_s,
+                    "iterations_per_solve": st["iterations"], "filtered_vecs_per_solve": st["filtered_vecs"],
+                    "phase_seconds_last_complete_solve": {k: st[k] for k in PHASES}})
     out["roofline"]["whole_run"] = whole_run_object(snapshot(), 1)
-    attach_traffic(out, args.workload)
-    attach_replay(out, args.workload)
-    if not args.no_probe and cplx:
-        # reference arithmetic (four real products per complex product, the reference's zgemm) on the same launch shape
-        out["roofline_4m"] = fullwidth_probe(s, ctx, N, cplx, nevex, three_m=False)
-        out["roofline_3m_fullwidth"] = fullwidth_probe(s, ctx, N, cplx, nevex, three_m=True)
-    # what THIS device's matrix pipe sustains in a bare register-resident MFMA loop right after the sustained load above
-    # (context for `frac`: the boxes of the pool differ by a few per cent on the 3M kernel; never its denominator)
-    try:
-        out["roofline"]["bare_mfma_loop_tflops_this_device"] = ctx.mfma_f64_peak()
-    except Exception as e:  # informative only
-        out["roofline"]["bare_mfma_loop_tflops_this_device"] = None
+    if args.full:
+        lam, resid = last
+        spec = spectrum_check(lam, N, nev)
+        # independent check outside the timed region (the reference's solve tests: tests/chase_serial_solve.cpp:144-148,
+        # 195-199): one fresh four-product H V over the nev eigenvectors of the last solve (a complete one) + the
+        # residual-norm kernel.  The solver's own residuals come from (H Q) A left behind by Rayleigh-Ritz,
+        # these from H itself.
+        resid_re = s.recompute_residuals(nev, lam)
+        out.update({"converged": converged_ok(lam, resid, resid_re, s.get("tol"), spec), "max_resid": float(np.max(resid)),
+                    "max_resid_recomputed": float(np.max(resid_re)),
+                    "residuals_rechecked_on_the_tolerance": int(s.get("resd_rechecked")), "spectrum_check": spec})
+        attach_traffic(out, args.workload)
+        attach_replay(out, args.workload)
+        if not args.no_probe and cplx:
+            # reference arithmetic (four real products per complex product, the reference's zgemm) on the same launch shape
+            out["roofline_4m"] = fullwidth_probe(s, ctx, N, cplx, nevex, three_m=False)
+            out["roofline_3m_fullwidth"] = fullwidth_probe(s, ctx, N, cplx, nevex, three_m=True)
+        # what THIS device's matrix pipe sustains in a bare register-resident MFMA loop right after the sustained load
+        # above (context for `frac`: the boxes of the pool differ by a few per cent on the 3M kernel; never its denominator)
+        try:
+            out["roofline"]["bare_mfma_loop_tflops_this_device"] = ctx.mfma_f64_peak()
+        except Exception:  # informative only
+            out["roofline"]["bare_mfma_loop_tflops_this_device"] = None
     s.close()
     del dH
     ctx.close()
@@ -743,8 +799,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS))
     ap.add_argument("--n", "--size", dest="n", type=int, default=0, help="override N (development only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probe", action="store_true", help="skip the full-width 4M / 3M kernel probes")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the CPU baseline, the parity guard on a complete solve, the full-width "
+                         "kernel probes and the recorded profile figures (a plain run measures the headline figure only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the solve hands its caller after the last timed step to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-probe", action="store_true", help="--full: skip the full-width 4M / 3M kernel probes")
     ap.add_argument("--cpu-budget", type=float, default=25.0)
     ap.add_argument("--dist", action="store_true",
                     help="run the grid Impl (pChaseHip) even on one GPU (1x1 grid; development: panel-pipeline overheads)")
@@ -788,6 +849,11 @@ def main():
         ap.error("need --steps >= 1 and --warmup >= 0")
     if args.workload is None:
         args.workload = DEFAULT_WORKLOAD
+    if args.dump_outputs and (args.gpus > 1 or args.dist or args.replay_rank or args.workload in PSEUDO_WORKLOADS
+                              or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs: only the single-GPU solve (--gpus 1, a Hermitian workload) writes its outputs")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if args.ranks == "processes":
         args.ranks = "bound"
     argv = [a for a in sys.argv[1:] if a != "--transport-probe"]

@@ -3,7 +3,7 @@
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_tr
-rocprofv3 --kernel-trace -f csv -d /tmp/prof_tr -o tr -- python3 $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline > /tmp/prof_tr.log 2>&1
+rocprofv3 --kernel-trace -f csv -d /tmp/prof_tr -o tr -- python3 $REPO/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline > /tmp/prof_tr.log 2>&1
 f=$(find /tmp/prof_tr -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'PY'
 import csv, sys, collections

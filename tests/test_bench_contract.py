@@ -25,8 +25,8 @@ class FakeSolver:
         self.calls += 1
         for it in range(self.iters):
             self.counters["it"] += 1
-            if self.hook and self.hook(it, 100 - it, it, self.iters - it):
-                self.aborted += 1
+            if self.hook and self.hook(it, 100 - it, it, self.iters - it) and it < self.iters - 1:
+                self.aborted += 1                          # (a stop on the last iteration ends the solve as usual)
                 return {"locked": 0, "t_all": 0.0}
         return {"locked": self.nev, "t_all": 1.0}
 
@@ -49,6 +49,63 @@ def test_step_timer_times_exactly_k_iterations(steps, warmup):
     total = warmup + steps
     assert s.calls == max(1, -(-total // s.iters))
     assert timer.filtered_timed == sum(100 - (i % s.iters) for i in range(warmup, total))
+
+
+@pytest.mark.parametrize("steps,warmup", [(6, 3), (20, 5), (1, 0), (9, 0), (2, 17), (4, 9), (9, 9)])
+@pytest.mark.parametrize("need_complete", [False, True])
+def test_cutting_timer_starts_the_timed_steps_with_a_fresh_solve(steps, warmup, need_complete):
+    """The single-GPU bench (StepTimer(cut=True)): the warm-up's solve ends with the last warm-up step, the timed steps are
+    the first K iterations of fresh solves, and the solve in flight ends with the last timed step; with need_complete (the
+    --full parity guard) one complete untimed solve follows when the timed steps ended inside a solve."""
+    s = FakeSolver()
+    events, dumped = [], []
+    timer = B.StepTimer(steps, warmup, lambda: events.append("sync"), lambda: events.append("barrier"),
+                        lambda: dict(s.counters), cut=True)
+    complete, last = B.run_timed_solves(s, timer, s.nev, lambda: ("lam", "res"),
+                                        after_timed=lambda: dumped.append(s.counters["it"]), need_complete=need_complete)
+    assert timer.done and timer.diff("it") == steps and timer.c0["it"] == warmup
+    assert len(timer.per_iter) == steps
+    assert events == ["sync", "sync", "barrier", "sync", "sync", "barrier"]
+    assert timer.filtered_timed == sum(100 - (i % s.iters) for i in range(steps))            # iterations 0.. of fresh solves
+    assert dumped == [warmup + steps]                                                         # right after the last timed step
+    warm_solves = -(-warmup // s.iters)
+    timed_solves = -(-steps // s.iters)
+    ends_inside = steps % s.iters != 0
+    extra = 1 if need_complete and ends_inside else 0
+    assert s.calls == warm_solves + timed_solves + extra
+    assert s.counters["it"] == warmup + steps + (s.iters if extra else 0)                   # nothing else ran
+    assert s.aborted == (warmup % s.iters != 0) + ends_inside
+    if need_complete:
+        assert len(complete) >= 1 and last == ("lam", "res")
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_size_limit(tmp_path):
+    import numpy as np
+    N, nev, nex = 65536, 2048, 512                                          # the headline workload's shapes
+    V = np.zeros((N, nev + nex), dtype=np.complex64, order="F")            # (complex64 only to keep this test light)
+    V[:, :nev] = (np.arange(N)[:, None] + 1j * np.arange(nev)[None, :]).astype(np.complex64)
+    ritzv, resid = np.linspace(-1, 1, nev + nex), np.full(nev + nex, 1e-11)
+    B.dump_outputs(str(tmp_path), N, nev, ritzv, resid, V)
+    B.dump_outputs(str(tmp_path / "again"), N, nev, ritzv, resid, V)
+    files = sorted(p.name for p in tmp_path.glob("*.npy"))
+    assert files == ["residuals.npy", "ritz_values.npy", "ritz_vectors_sample.npy", "ritz_vectors_sample_rows.npy"]
+    assert sum(p.stat().st_size for p in tmp_path.glob("*.npy")) <= 64 << 20
+    for f in files:
+        a, b = np.load(tmp_path / f), np.load(tmp_path / "again" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)              # the sample is fixed and seeded
+    rows = np.load(tmp_path / "ritz_vectors_sample_rows.npy").astype(np.int64)
+    vs = np.load(tmp_path / "ritz_vectors_sample.npy")
+    assert vs.shape == (B.DUMP_ROWS, nev, 2) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(vs[:, :, 0], np.broadcast_to(rows[:, None], (B.DUMP_ROWS, nev)))
+    assert np.array_equal(vs[:, :, 1], np.broadcast_to(np.arange(nev)[None, :], (B.DUMP_ROWS, nev)))
+    assert np.array_equal(np.load(tmp_path / "ritz_values.npy"), ritzv)
+
+
+def test_dump_outputs_is_refused_where_no_single_gpu_solve_runs(tmp_path):
+    for extra in (["--gpus", "2"], ["--workload", "cfg5"], ["--dist"]):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", str(tmp_path), *extra],
+                           capture_output=True, text=True, timeout=120)
+        assert p.returncode == 2 and "--dump-outputs" in p.stderr, extra
 
 
 def test_a_solves_seconds_exclude_what_its_hooks_waited_for():

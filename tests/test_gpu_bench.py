@@ -38,7 +38,7 @@ def check_common(d, n_gpus, steps, warmup):
 
 
 def test_single_gpu_line_keeps_the_contract():
-    d = run_bench("--workload", "cfg2", "--steps", "9", "--warmup", "0", "--cpu-budget", "3")
+    d = run_bench("--workload", "cfg2", "--steps", "9", "--warmup", "0", "--cpu-budget", "3", "--full")
     check_common(d, 1, 9, 0)
     # the oracle's solve of config 2 at full size (tests/golden/oracle_cfg2_fullsize.json; the single-GPU Impl takes it count for
     # count from the oracle's matrix and start block, tests/test_gpu_fullsize.py): the bench workload differs from it by the
@@ -54,6 +54,30 @@ def test_single_gpu_line_keeps_the_contract():
     for probe in ("roofline_4m", "roofline_3m_fullwidth"):
         assert 0.0 < d[probe]["frac"] <= 1.0
     assert d["roofline"]["executed_over_model"] == pytest.approx(0.75, abs=0.02)             # 3M filter products
+
+
+def test_plain_single_gpu_run_is_lean_and_dumps_what_the_timed_steps_computed(tmp_path):
+    """A plain run (no --full): the headline figure of K timed iterations after W warm-up ones and nothing else - no CPU
+    baseline, no kernel probes, no extra solve; --dump-outputs writes the state after the last timed step, the same from
+    run to run (seeded matrix and start block)."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        d = run_bench("--workload", "cfg2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / str(i)))
+        assert d["metric"] == "chebyshev_filter_hemm_gflops" and d["unit"] == "GFLOP/s" and d["higher_is_better"] is True
+        assert (d["n_gpus"], d["steps"], d["warmup"], d["full"]) == (1, 3, 1, False) and d["dtype"] == "complex f64"
+        assert d["value"] > 0 and d["ms_per_step"] > 0 and 0.0 < d["roofline"]["frac"] <= 1.0
+        assert [(t["solve"], t["iteration"]) for t in d["timed"]["iterations"]] == [(1, 0), (1, 1), (1, 2)]
+        assert d["complete_solves"] == 0
+        for k in ("cpu_baseline", "roofline_4m", "roofline_3m_fullwidth", "converged", "spectrum_check"):
+            assert k not in d, k
+        runs.append({f.name: np.load(f) for f in (tmp_path / str(i)).glob("*.npy")})
+    a, b = runs
+    assert sorted(a) == ["residuals.npy", "ritz_values.npy", "ritz_vectors_sample.npy", "ritz_vectors_sample_rows.npy"]
+    assert a["ritz_values.npy"].shape == (640,) and a["ritz_vectors_sample.npy"].shape == (1024, 512, 2)
+    for k in a:
+        assert a[k].dtype == np.float64 and np.all(np.isfinite(a[k]))
+        assert np.allclose(a[k], b[k], rtol=1e-10, atol=1e-12), k
 
 
 def test_multi_rank_entry_point_on_one_gpu():
