@@ -390,6 +390,36 @@ def gemm_counters(ctx, phase, reset=False):
     return a.value, b.value, n.value
 
 
+class GemmLaunch(C.Structure):
+    """One launch of a product (chase_hip_gemm_launch)."""
+    _fields_ = [(f, c_int) for f in ("row0", "col0", "k0", "m", "n", "k", "beta_one", "bn_cols", "narrow", "m3", "ragged",
+                                     "glds_ok", "gm", "gn")] + \
+               [("full_tiles", c_long), ("tail_tiles", c_long)] + \
+               [(f, c_int) for f in ("tail_sk", "tail_kchunk", "group_rows", "forced_split")] + \
+               [("slab_bytes", c_size_t), ("plane_bytes", c_size_t)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+_sig("chase_hip_gemm_plan", c_int, c_int, c_char, c_int, c_int, c_int, c_long, c_long, c_int, c_int, c_int, c_int,
+     P(GemmLaunch), c_int)
+
+
+def gemm_plan(cplx, op, m, n, k, lda=None, ldb=None, aligned=True, phase=0, num_cu=256, min_rounds=0):
+    """The launches chase_hip_gemm_{d,z} makes for this product, as dicts (chase_hip_gemm_plan; host-only).  lda / ldb default
+    to the tightest leading dimensions."""
+    lda = (m if op == "N" else k) if lda is None else lda
+    ldb = k if ldb is None else ldb
+    args = (int(cplx), op.encode(), m, n, k, max(lda, 1), max(ldb, 1), int(aligned), phase, num_cu, min_rounds)
+    cnt = lib.chase_hip_gemm_plan(*args, None, 0)
+    if cnt < 0:
+        check(cnt, "gemm_plan")
+    out = (GemmLaunch * max(cnt, 1))()
+    assert lib.chase_hip_gemm_plan(*args, out, cnt) == cnt
+    return [out[i].as_dict() for i in range(cnt)]
+
+
 class Solver:
     """ChaseHip<T> behind the C ABI: the reference's ChASEGPU constructor contract (host H, V, ritzv owned by the
     caller; chase_gpu.hpp:107) plus chase::Solve."""

@@ -260,6 +260,15 @@ size_t chase_hip_gemm_workspace_bytes(int cplx, char opA, int m, int n, int k, i
 {
     return gemm_f64_ws_need(cplx != 0, opA, m, n, k, num_cu, min_rounds);
 }
+int chase_hip_gemm_plan(int cplx, char opA, int m, int n, int k, long lda, long ldb, int aligned16, int phase, int num_cu,
+                        int min_rounds, chase_hip_gemm_launch* out, int max_out)
+{
+    const bool opn = (opA == 'N' || opA == 'n'), opc = (opA == 'C' || opA == 'c' || opA == 'T' || opA == 't');
+    if (!opn && !opc) return set_error(CHASE_HIP_EINVAL, "gemm_plan: opA must be 'N' or 'C'");
+    if (m < 0 || n < 0 || k < 0 || num_cu <= 0 || max_out < 0) return set_error(CHASE_HIP_EINVAL, "gemm_plan: bad argument");
+    return gemm_f64_plan(cplx != 0, opA, m, n, k, lda, ldb, aligned16 != 0, phase, num_cu, min_rounds < 0 ? 0 : min_rounds, out,
+                         max_out);
+}
 int chase_hip_gemm3m_enabled(void) { return gemm3m_enabled(); }
 int chase_hip_set_gemm3m(int on)
 {

@@ -43,6 +43,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <type_traits>
+#include "../../include/chase_hip.h"
 #include "kernels.h"
 
 #ifndef CHASE_M3_PIPELINE
@@ -1084,7 +1085,7 @@ constexpr int MAX_DEVICES = 64;
 // pieces, the slab bytes that needs.  A function of the shape, the chip and min_rounds ONLY - the split, and with it the
 // summation order, never depends on how far a caller's workspace happens to have grown.  The one place both the launcher
 // (launch_gemm_part) and the workspace sizing (gemm_f64_ws_need) take it from.
-struct PartPlan { long full, tail; int sk; size_t ws_bytes; };
+struct PartPlan { long full, tail; int sk; size_t ws_bytes; bool forced = false; };   // forced: the split is forced_split's
 template <bool CPLX, bool OPA_C, bool NARROW = false>
 static PartPlan plan_part(int m, int n, int k, int bn_cols, int num_cu, int min_rounds)
 {
@@ -1097,7 +1098,7 @@ static PartPlan plan_part(int m, int n, int k, int bn_cols, int num_cu, int min_
     PartPlan p{tiles, 0, 1, 0};
     if (m <= 0 || n <= 0 || k <= 0) return p;
     const int fs = forced_split(tiles, slots, nkt, slab_bytes, min_rounds);
-    if (fs > 1) { p.full = 0; p.tail = tiles; p.sk = fs; }  // shared-chip launch: every tile in K pieces
+    if (fs > 1) { p.full = 0; p.tail = tiles; p.sk = fs; p.forced = true; }   // shared-chip launch: every tile in K pieces
     else {
         // cost of the tail in units of "one tile on one slot": ceil(tail*sk/slots)/sk rounds, slightly penalising big sk
         const long tail = tiles % slots;
@@ -1162,6 +1163,59 @@ static ColsPlan plan_cols(int m, int n, int k, bool have_ws)
     }
 }
 
+// Everything ONE launch decides (launch_gemm_part): tile stride, tile order, work decomposition, 3M or 4M, the copy path, the
+// workspace it needs.  A host-only function of the piece's shape, its operands' alignment and leading dimensions, the chip,
+// min_rounds and the run-time switches - the launcher and the plan query (gemm_f64_plan) both take it from here, so the query
+// cannot drift from what runs.
+struct PartDecision {
+    int gm, gn, bn_cols, group_rows;
+    PartPlan pl;                  // whole tiles, tail tiles, their K split, the slab bytes
+    int kchunk;                   // K per tail piece
+    bool glds_ok, ragged, m3;
+    size_t plane_bytes;           // operand-sum plane of a 3M launch: behind the slabs, at the next 256-byte boundary
+};
+template <bool CPLX, bool OPA_C, bool NARROW>
+static PartDecision decide_part(int m, int n, int k, long lda, long ldb, bool aligned16, bool have_ws, int num_cu,
+                                bool allow3m, int min_rounds, int bn_cols)
+{
+    using C_ = Cfg<CPLX, OPA_C, NARROW>;
+    PartDecision d;
+    if (bn_cols <= 0 || bn_cols > C_::BN) bn_cols = C_::BN;
+    d.bn_cols = bn_cols;
+    d.gm = (m + C_::BM - 1) / C_::BM; d.gn = (n + bn_cols - 1) / bn_cols;
+    // Row panels per group of the tile order (tile_coords): 2; FOUR for launches of many rounds with many column tiles (round 6).
+    // With the plane-fed 3M loop the workgroups that share panels stay in step, so a 4 x 16 patch of tiles per XCD (256 KB of
+    // unique operands per K step instead of 416 KB) really is served by the L2: 0.89 instead of 1.31 TB through the fabric for
+    // the full-width config-4 launch, the same time on a device that holds its clock (873 vs 875 ms) and 2 % less on one that
+    // does not under this load (877 vs 892-898 ms: profiles/r06_tile_group.txt).  Short launches and the 256-column panels of the
+    // grid pipeline (4 column tiles) are 2.5 % SLOWER with 4, hence the rule - a function of the shape and of num_cu (the order
+    // decides which tiles form the K-split tail, i.e. the summation order: devices with another CU count may order differently).
+    // CHASE_HIP_TILE_GROUP=<n> fixes it for every launch.
+    static const int group_env = [] { const char* e = getenv("CHASE_HIP_TILE_GROUP"); const int v = e ? atoi(e) : 0; return v < 0 ? 0 : v; }();
+    d.group_rows = group_env > 0 ? group_env : ((d.gn >= 16 && (long)d.gm * d.gn >= 16L * 2 * num_cu) ? 4 : 2);
+    const int nkt = (k + C_::BK - 1) / C_::BK;
+    // without a workspace nothing can be split; with one, the launcher refuses a workspace smaller than the plan's slabs -
+    // callers size it with gemm_f64_ws_need, which takes its numbers from the same plan
+    d.pl = plan_part<CPLX, OPA_C, NARROW>(m, n, k, bn_cols, num_cu, min_rounds);
+    if (!have_ws) d.pl = PartPlan{(long)d.gm * d.gn, 0, 1, 0};
+    d.kchunk = ((nkt + d.pl.sk - 1) / d.pl.sk) * C_::BK;
+    // global_load_lds moves 16 bytes per lane: complex elements always qualify, real ones need even leading dimensions
+    d.glds_ok = aligned16 && (CPLX || ((lda % 2 == 0) && (ldb % 2 == 0))) &&
+                (double)std::max(lda, ldb) * C_::BM * C_::EPT * 8 < 4.0e9;      // per-lane byte offsets are 32-bit
+    // ragged: some 16-column group of the last column tile lies entirely past n
+    d.ragged = (bn_cols < C_::BN) || (d.gn * C_::BN - n) >= 16;
+    // complex HEMMs of the filter phase (tag 1) and the H-times-block products of Rayleigh-Ritz / residuals (tag 2, see
+    // gemm_f64) run the 3-product scheme unless CHASE_HIP_GEMM3M=0 / gemm3m_set(0); everything else - Gram products,
+    // back-transforms, QR, verification products (tag 3) - stays on four products like the reference's zgemm.
+    // The 3M instantiation has no register-staged fallback: whole row tiles, whole K tiles, 16-byte addressable operands;
+    // k = 0 (C = beta C, nothing to multiply) stays on four: the operand-sum plane of an empty K range would be a launch of
+    // zero workgroups.  Its plane sits in the workspace, so without one: four products.
+    d.m3 = CPLX && allow3m && gemm3m_enabled() != 0 && d.glds_ok && k > 0 && (m % C_::BM == 0) && (k % C_::BK == 0) &&
+           (d.kchunk % C_::BK == 0) && (!CHASE_M3_SPLANE || have_ws);
+    d.plane_bytes = (d.m3 && CHASE_M3_SPLANE) ? splane_bytes(n, k, bn_cols) : 0;
+    return d;
+}
+
 template <bool CPLX, bool OPA_C, int TAG, bool NARROW = false>
 static int launch_gemm_part(hipStream_t st, int m, int n, int k, const double* alpha, const double* A, long lda,
                             const double* B, long ldb, const double* beta, double* C, long ldc,
@@ -1170,42 +1224,23 @@ static int launch_gemm_part(hipStream_t st, int m, int n, int k, const double* a
 {
     using C_ = Cfg<CPLX, OPA_C, NARROW>;
     if (m <= 0 || n <= 0) return 0;
-    if (bn_cols <= 0 || bn_cols > C_::BN) bn_cols = C_::BN;
+    const PartDecision d = decide_part<CPLX, OPA_C, NARROW>(m, n, k, lda, ldb, (((uintptr_t)A | (uintptr_t)B) % 16 == 0),
+                                                            ws != nullptr, num_cu, allow3m, li.min_rounds, bn_cols);
+    if (d.pl.ws_bytes > ws_bytes) return GEMM_F64_EWORKSPACE;           // never split differently to fit: refuse (distinct code)
     GemmArgs a;
     a.A = A; a.B = B; a.C = C; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.m = m; a.n = n; a.k = k;
-    a.gm = (m + C_::BM - 1) / C_::BM; a.gn = (n + bn_cols - 1) / bn_cols;
-    a.bn_cols = bn_cols;
-    // Row panels per group of the tile order (tile_coords): 2; FOUR for launches of many rounds with many column tiles (round 6).
-    // With the plane-fed 3M loop the workgroups that share panels stay in step, so a 4 x 16 patch of tiles per XCD (256 KB of
-    // unique operands per K step instead of 416 KB) really is served by the L2: 0.89 instead of 1.31 TB through the fabric for
-    // the full-width config-4 launch, the same time on a device that holds its clock (873 vs 875 ms) and 2 % less on one that
-    // does not under this load (877 vs 892-898 ms: profiles/r06_tile_group.txt).  Short launches and the 256-column panels of the
-    // grid pipeline (4 column tiles) are 2.5 % SLOWER with 4, hence the rule - a function of the shape alone (the order decides
-    // which tiles form the K-split tail, i.e. the summation order, which must not depend on the device).
-    // CHASE_HIP_TILE_GROUP=<n> fixes it for every launch.
-    static const int group_env = [] { const char* e = getenv("CHASE_HIP_TILE_GROUP"); const int v = e ? atoi(e) : 0; return v < 0 ? 0 : v; }();
-    a.group_rows = group_env > 0 ? group_env : ((a.gn >= 16 && (long)a.gm * a.gn >= 16L * 2 * num_cu) ? 4 : 2);
+    a.gm = d.gm; a.gn = d.gn; a.bn_cols = d.bn_cols; a.group_rows = d.group_rows;
     a.alpha_re = alpha[0]; a.alpha_im = CPLX ? alpha[1] : 0.0;
     a.beta_re = beta[0];   a.beta_im = CPLX ? beta[1] : 0.0;
-    const int nkt = (k + C_::BK - 1) / C_::BK;
-    // without a workspace nothing can be split; with one, the plan's slabs must fit - callers size the workspace with
-    // gemm_f64_ws_need, which takes its numbers from the same plan
-    PartPlan pl = plan_part<CPLX, OPA_C, NARROW>(m, n, k, bn_cols, num_cu, li.min_rounds);
-    if (ws == nullptr) pl = PartPlan{(long)a.gm * a.gn, 0, 1, 0};
-    if (pl.ws_bytes > ws_bytes) return GEMM_F64_EWORKSPACE;             // never split differently to fit: refuse (distinct code)
-    const long full = pl.full, tail = pl.tail;
-    const int sk = pl.sk;
-    int kchunk = ((nkt + sk - 1) / sk) * C_::BK;
-    a.full_tiles = (int)full; a.tail_sk = sk; a.tail_kchunk = kchunk; a.slabs = ws;
-    // global_load_lds moves 16 bytes per lane: complex elements always qualify, real ones need even leading dimensions
-    a.glds_ok = (((uintptr_t)A | (uintptr_t)B) % 16 == 0) && (CPLX || ((lda % 2 == 0) && (ldb % 2 == 0))) &&
-                (double)std::max(lda, ldb) * C_::BM * C_::EPT * 8 < 4.0e9;      // per-lane byte offsets are 32-bit
+    const long full = d.pl.full, tail = d.pl.tail;
+    const int sk = d.pl.sk;
+    a.full_tiles = (int)full; a.tail_sk = sk; a.tail_kchunk = d.kchunk; a.slabs = ws;
+    a.glds_ok = d.glds_ok;
     const unsigned grid = (unsigned)(full + tail * sk);
     const size_t lds_bytes = (size_t)C_::STAGES * C_::STAGE_UNITS * sizeof(d2_t);
     // 3M kernels: + the ring of two 4 KB stages of the operand-sum plane (80 KB: two workgroups per CU still fit)
     const size_t lds_bytes3 = lds_bytes + (CHASE_M3_SPLANE ? 2 * 4096 : 0);
-    // ragged: some 16-column group of the last column tile lies entirely past n
-    const bool ragged = (bn_cols < C_::BN) || (a.gn * C_::BN - n) >= 16;
+    const bool ragged = d.ragged;
     // the dynamic-LDS limit is a per-device function attribute: one flag per device (setting it twice is harmless, so a
     // relaxed atomic is enough for concurrent first calls)
     const int dev = (li.device >= 0 && li.device < MAX_DEVICES) ? li.device : 0;
@@ -1215,13 +1250,8 @@ static int launch_gemm_part(hipStream_t st, int m, int n, int k, const double* a
         (void)hipFuncSetAttribute((const void*)gemm_f64_kernel<CPLX, OPA_C, TAG, true, false, NARROW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         attr_set[dev].store(true, std::memory_order_relaxed);
     }
-    // complex HEMMs of the filter phase (tag 1) and the H-times-block products of Rayleigh-Ritz / residuals (tag 2, see
-    // gemm_f64) run the 3-product scheme unless CHASE_HIP_GEMM3M=0 / gemm3m_set(0); everything else - Gram products,
-    // back-transforms, QR, verification products (tag 3) - stays on four products like the reference's zgemm
     constexpr bool CAN3M = CPLX;
-    const bool want3m = gemm3m_enabled() != 0;
-    // the 3M instantiation has no register-staged fallback: whole row tiles, whole K tiles, 16-byte addressable operands
-    bool ok3m = allow3m && want3m && a.glds_ok && (m % C_::BM == 0) && (k % C_::BK == 0) && (kchunk % C_::BK == 0);
+    const bool ok3m = d.m3;
     a.S = nullptr; a.s_nkt = 0;
     if constexpr (CAN3M) {
         static std::atomic<bool> attr3[MAX_DEVICES];
@@ -1233,15 +1263,12 @@ static int launch_gemm_part(hipStream_t st, int m, int n, int k, const double* a
         if (ok3m && CHASE_M3_SPLANE) {
             // the operand-sum plane sits behind the slabs in the caller's workspace (gemm_f64_ws_need counts it); written on the
             // same stream right before the product
-            const size_t off = (pl.ws_bytes + 255) & ~(size_t)255, sb = splane_bytes(n, k, bn_cols);
-            if (ws == nullptr) ok3m = false;                                   // no workspace: four products
-            else if (off + sb > ws_bytes) return GEMM_F64_EWORKSPACE;
-            else {
-                double* S = (double*)((char*)ws + off);
-                hipLaunchKernelGGL(splane_kernel, dim3((unsigned)((k + 63) / 64), (unsigned)a.gn), dim3(256), 0, st, B, ldb, n, k,
-                                   bn_cols, k / C_::BK, S);
-                a.S = S; a.s_nkt = k / C_::BK;
-            }
+            const size_t off = (d.pl.ws_bytes + 255) & ~(size_t)255;
+            if (off + d.plane_bytes > ws_bytes) return GEMM_F64_EWORKSPACE;
+            double* S = (double*)((char*)ws + off);
+            hipLaunchKernelGGL(splane_kernel, dim3((unsigned)((k + 63) / 64), (unsigned)a.gn), dim3(256), 0, st, B, ldb, n, k,
+                               d.bn_cols, k / C_::BK, S);
+            a.S = S; a.s_nkt = k / C_::BK;
         }
         if (ok3m) {
             if (ragged) hipLaunchKernelGGL((gemm_f64_kernel<CPLX, OPA_C, TAG, true, CAN3M>), dim3(grid), dim3(256), lds_bytes3, st, a);
@@ -1286,33 +1313,6 @@ static int uniform_tile_cols(int m, int n, int k)
     return 0;
 }
 
-// A ragged last column tile (n % BN != 0) is cheap only next to its own kind: the matrix-core arbiter favours the older
-// wave, so a partial-tile workgroup sharing a CU with a whole-tile one advances at the whole tile's pace (measured: no
-// gain from skipped MFMAs when mixed).  The ragged column therefore gets its own launch, K-split over the whole chip,
-// where every workgroup skips the same 16-column groups.
-template <bool CPLX, bool OPA_C, int TAG>
-static int launch_gemm_cols(hipStream_t st, int m, int n, int k, const double* alpha, const double* A, long lda,
-                            const double* B, long ldb, const double* beta, double* C, long ldc,
-                            double* ws, size_t ws_bytes, int num_cu, bool allow3m, const LaunchInfo& li)
-{
-    constexpr int EPT = CPLX ? 2 : 1;
-    const ColsPlan cp = plan_cols<CPLX, OPA_C>(m, n, k, ws != nullptr);
-    for (int i = 0; i < cp.npieces; ++i) {
-        const ColPiece& pc = cp.piece[i];
-        const double* Bp = B + (long)pc.c0 * ldb * EPT;
-        double* Cp = C + (long)pc.c0 * ldc * EPT;
-        int rc;
-        if constexpr (!CPLX) {
-            if (pc.narrow) rc = launch_gemm_part<CPLX, OPA_C, TAG, true>(st, m, pc.n, k, alpha, A, lda, Bp, ldb, beta, Cp, ldc, ws, ws_bytes, num_cu, allow3m, li, pc.bn_cols);
-            else           rc = launch_gemm_part<CPLX, OPA_C, TAG, false>(st, m, pc.n, k, alpha, A, lda, Bp, ldb, beta, Cp, ldc, ws, ws_bytes, num_cu, allow3m, li, pc.bn_cols);
-        } else {
-            rc = launch_gemm_part<CPLX, OPA_C, TAG, false>(st, m, pc.n, k, alpha, A, lda, Bp, ldb, beta, Cp, ldc, ws, ws_bytes, num_cu, allow3m, li, pc.bn_cols);
-        }
-        if (rc) return rc;
-    }
-    return 0;
-}
-
 // The three-multiplication kernel has no guarded path: it needs whole 128-row tiles and whole 8-deep K tiles.  A filter
 // product of ARBITRARY size (N = 1001, a local block of 8193 rows ...) is therefore cut into the part that qualifies,
 //   C[0:m1, :] = alpha op(A)[0:m1, 0:k1] B[0:k1, :] + beta C[0:m1, :]        m1 = m - m mod 128, k1 = k - k mod 8   (3M)
@@ -1329,30 +1329,55 @@ static bool split3m_applies(int m, int n, int k, bool allow3m)
     return m >= 8 * C_::BM && k >= 64 * C_::BK && n >= 16;             // the rims must be thin next to the bulk
 }
 
+// One launch of a product: rows [r0, r0 + m) and columns [c0, c0 + n) of C from the K range [k0, k0 + k) of op(A);
+// beta_one: a K rim, which adds into what the bulk wrote before it (beta = 1) instead of applying the caller's beta.
+struct Piece { int r0, c0, k0, m, n, k, bn_cols; bool narrow, beta_one, allow3m; };
+
+// The launches of a product in launch order, f(piece) each (a nonzero return stops the walk and is returned): the 3M bulk and
+// its 4M rims (split3m_applies), and each of those as at most two column pieces (plan_cols).
+// A ragged last column tile (n % BN != 0) is cheap only next to its own kind: the matrix-core arbiter favours the older
+// wave, so a partial-tile workgroup sharing a CU with a whole-tile one advances at the whole tile's pace (measured: no
+// gain from skipped MFMAs when mixed).  The ragged column therefore gets its own launch, K-split over the whole chip,
+// where every workgroup skips the same 16-column groups.
+template <bool CPLX, bool OPA_C, class F>
+static int for_each_piece(int m, int n, int k, bool have_ws, bool allow3m, F&& f)
+{
+    auto cols = [&](int r0, int k0, int mm, int kk, bool beta_one, bool a3) {
+        const ColsPlan cp = plan_cols<CPLX, OPA_C>(mm, n, kk, have_ws);
+        for (int i = 0; i < cp.npieces; ++i) {
+            const ColPiece& pc = cp.piece[i];
+            if (const int rc = f(Piece{r0, pc.c0, k0, mm, pc.n, kk, pc.bn_cols, pc.narrow, beta_one, a3})) return rc;
+        }
+        return 0;
+    };
+    if (!split3m_applies<CPLX, OPA_C>(m, n, k, allow3m)) return cols(0, 0, m, k, false, allow3m);
+    using C_ = Cfg<CPLX, OPA_C>;
+    const int m1 = m - m % C_::BM, k1 = k - k % C_::BK;
+    int rc = cols(0, 0, m1, k1, false, true);
+    if (rc == 0 && k1 < k) rc = cols(0, k1, m1, k - k1, true, false);
+    if (rc == 0 && m1 < m) rc = cols(m1, 0, m - m1, k, false, false);
+    return rc;
+}
+
 template <bool CPLX, bool OPA_C, int TAG>
 static int launch_gemm(hipStream_t st, int m, int n, int k, const double* alpha, const double* A, long lda,
                        const double* B, long ldb, const double* beta, double* C, long ldc,
                        double* ws, size_t ws_bytes, int num_cu, bool allow3m, const LaunchInfo& li)
 {
-    using C_ = Cfg<CPLX, OPA_C>;
-    constexpr int EPT = C_::EPT;
-    if (!split3m_applies<CPLX, OPA_C>(m, n, k, allow3m))
-        return launch_gemm_cols<CPLX, OPA_C, TAG>(st, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, ws, ws_bytes, num_cu, allow3m, li);
-    const int m1 = m - m % C_::BM, k1 = k - k % C_::BK;
-    // element (i, kk) of op(A): op = N: A[i + kk lda];  op = C: conj(A[kk + i lda])
-    auto Aoff = [&](int i, int kk) { return A + (OPA_C ? ((long)i * lda + kk) : ((long)kk * lda + i)) * EPT; };
+    constexpr int EPT = CPLX ? 2 : 1;
     const double one[2] = {1.0, 0.0};
-    int rc = launch_gemm_cols<CPLX, OPA_C, TAG>(st, m1, n, k1, alpha, A, lda, B, ldb, beta, C, ldc, ws, ws_bytes, num_cu, true, li);
-    if (rc) return rc;
-    if (k1 < k) {
-        rc = launch_gemm_cols<CPLX, OPA_C, TAG>(st, m1, n, k - k1, alpha, Aoff(0, k1), lda, B + (long)k1 * EPT, ldb, one, C, ldc,
-                                                ws, ws_bytes, num_cu, false, li);
-        if (rc) return rc;
-    }
-    if (m1 < m)
-        rc = launch_gemm_cols<CPLX, OPA_C, TAG>(st, m - m1, n, k, alpha, Aoff(m1, 0), lda, B, ldb, beta, C + (long)m1 * EPT, ldc,
-                                                ws, ws_bytes, num_cu, false, li);
-    return rc;
+    return for_each_piece<CPLX, OPA_C>(m, n, k, ws != nullptr, allow3m, [&](const Piece& pc) {
+        // element (i, kk) of op(A): op = N: A[i + kk lda];  op = C: conj(A[kk + i lda])
+        const double* Ap = A + (OPA_C ? ((long)pc.r0 * lda + pc.k0) : ((long)pc.k0 * lda + pc.r0)) * EPT;
+        const double* Bp = B + ((long)pc.c0 * ldb + pc.k0) * EPT;
+        double* Cp = C + ((long)pc.c0 * ldc + pc.r0) * EPT;
+        const double* bp = pc.beta_one ? one : beta;
+        if constexpr (!CPLX) {
+            if (pc.narrow)
+                return launch_gemm_part<CPLX, OPA_C, TAG, true>(st, pc.m, pc.n, pc.k, alpha, Ap, lda, Bp, ldb, bp, Cp, ldc, ws, ws_bytes, num_cu, pc.allow3m, li, pc.bn_cols);
+        }
+        return launch_gemm_part<CPLX, OPA_C, TAG, false>(st, pc.m, pc.n, pc.k, alpha, Ap, lda, Bp, ldb, bp, Cp, ldc, ws, ws_bytes, num_cu, pc.allow3m, li, pc.bn_cols);
+    });
 }
 
 // bytes of split-K workspace this product can use (0: none): the slabs of the tail tiles at the split that minimises the
@@ -1400,24 +1425,71 @@ size_t gemm_f64_ws_need(bool cplx, char opA, int m, int n, int k, int num_cu, in
     return r;
 }
 
+// tag 2 = the H-times-block products of Rayleigh-Ritz and of the residual step: three multiplications like the filter (tag 1)
+// since round 4 (the residuals that decide locking are re-taken from a fresh four-product H v whenever they come within 1e-3 of
+// the tolerance, chase_hip_impl.hpp Resd; CHASE_HIP_GEMM3M_RR=0 restores four products); tag 3 = verification products
+// (recompute_residuals, the borderline re-check) and tag 0: four multiplications, always
+static bool tag_allows3m(int tag)
+{
+    static const bool rr3m = [] { const char* e = getenv("CHASE_HIP_GEMM3M_RR"); return e ? atoi(e) != 0 : true; }();
+    return tag == 1 || (tag == 2 && rr3m);
+}
+
 int gemm_f64(hipStream_t st, bool cplx, char opA, int m, int n, int k, const double* alpha, const double* A, long lda,
              const double* B, long ldb, const double* beta, double* C, long ldc, double* ws, size_t ws_bytes, int num_cu,
              int tag, int device, double* exec_flops, int min_rounds)
 {
     const bool opc = (opA == 'C' || opA == 'c' || opA == 'T' || opA == 't');
     const LaunchInfo li{device, exec_flops, min_rounds};
-    // tag 2 = the H-times-block products of Rayleigh-Ritz and of the residual step: three multiplications like the filter
-    // since round 4 (the residuals that decide locking are re-taken from a fresh four-product H v whenever they come within
-    // 1e-3 of the tolerance, chase_hip_impl.hpp Resd; CHASE_HIP_GEMM3M_RR=0 restores four products); tag 3 = verification
-    // products (recompute_residuals, the borderline re-check): four multiplications, always
-    static const bool rr3m = [] { const char* e = getenv("CHASE_HIP_GEMM3M_RR"); return e ? atoi(e) != 0 : true; }();
-    const bool allow2 = (tag == 2) && rr3m;
+    const bool allow3m = tag_allows3m(tag);
 #define CHASE_GEMM_DISPATCH(CP, OC)                                                                                    \
-    (tag == 1 ? launch_gemm<CP, OC, 1>(st, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, ws, ws_bytes, num_cu, true, li) \
-              : launch_gemm<CP, OC, 0>(st, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, ws, ws_bytes, num_cu, allow2, li))
+    (tag == 1 ? launch_gemm<CP, OC, 1>(st, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, ws, ws_bytes, num_cu, allow3m, li) \
+              : launch_gemm<CP, OC, 0>(st, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, ws, ws_bytes, num_cu, allow3m, li))
     if (!cplx) return opc ? CHASE_GEMM_DISPATCH(false, true) : CHASE_GEMM_DISPATCH(false, false);
     return opc ? CHASE_GEMM_DISPATCH(true, true) : CHASE_GEMM_DISPATCH(true, false);
 #undef CHASE_GEMM_DISPATCH
+}
+
+// The launches gemm_f64 makes for a product, without making them: the same piece walk and the same per-launch decisions
+// (for_each_piece, decide_part) with the workspace a context always has
+template <bool CPLX, bool OPA_C>
+static int plan_query(int m, int n, int k, long lda, long ldb, bool aligned16, bool allow3m, int num_cu, int min_rounds,
+                      chase_hip_gemm_launch* out, int max_out)
+{
+    constexpr int EPT = CPLX ? 2 : 1;
+    int cnt = 0;
+    for_each_piece<CPLX, OPA_C>(m, n, k, true, allow3m, [&](const Piece& pc) {
+        if (pc.m <= 0 || pc.n <= 0) return 0;                                 // launch_gemm_part launches nothing
+        // the piece's operands start at these element offsets from the caller's A and B (launch_gemm)
+        const long aoff = OPA_C ? (long)pc.r0 * lda + pc.k0 : (long)pc.k0 * lda + pc.r0, boff = (long)pc.c0 * ldb + pc.k0;
+        const bool al = aligned16 && (((aoff | boff) * EPT * 8) % 16 == 0);
+        PartDecision d;
+        if (!CPLX && pc.narrow) d = decide_part<CPLX, OPA_C, !CPLX>(pc.m, pc.n, pc.k, lda, ldb, al, true, num_cu, pc.allow3m, min_rounds, pc.bn_cols);
+        else                    d = decide_part<CPLX, OPA_C, false>(pc.m, pc.n, pc.k, lda, ldb, al, true, num_cu, pc.allow3m, min_rounds, pc.bn_cols);
+        if (out && cnt < max_out) {
+            chase_hip_gemm_launch& r = out[cnt];
+            r.row0 = pc.r0; r.col0 = pc.c0; r.k0 = pc.k0; r.m = pc.m; r.n = pc.n; r.k = pc.k;
+            r.beta_one = pc.beta_one; r.bn_cols = d.bn_cols; r.narrow = pc.narrow; r.m3 = d.m3; r.ragged = d.ragged;
+            r.glds_ok = d.glds_ok; r.gm = d.gm; r.gn = d.gn; r.full_tiles = d.pl.full; r.tail_tiles = d.pl.tail;
+            r.tail_sk = d.pl.sk; r.tail_kchunk = d.kchunk; r.group_rows = d.group_rows; r.forced_split = d.pl.forced;
+            r.slab_bytes = d.pl.ws_bytes; r.plane_bytes = d.plane_bytes;
+        }
+        ++cnt;
+        return 0;
+    });
+    return cnt;
+}
+
+int gemm_f64_plan(bool cplx, char opA, int m, int n, int k, long lda, long ldb, bool aligned16, int tag, int num_cu, int min_rounds,
+                  chase_hip_gemm_launch* out, int max_out)
+{
+    const bool opc = (opA == 'C' || opA == 'c' || opA == 'T' || opA == 't');
+    if (m <= 0 || n <= 0) return 0;                                          // chase_hip_ctx::gemm launches nothing
+    const bool a3 = tag_allows3m(tag);
+    if (!cplx) return opc ? plan_query<false, true>(m, n, k, lda, ldb, aligned16, a3, num_cu, min_rounds, out, max_out)
+                          : plan_query<false, false>(m, n, k, lda, ldb, aligned16, a3, num_cu, min_rounds, out, max_out);
+    return opc ? plan_query<true, true>(m, n, k, lda, ldb, aligned16, a3, num_cu, min_rounds, out, max_out)
+               : plan_query<true, false>(m, n, k, lda, ldb, aligned16, a3, num_cu, min_rounds, out, max_out);
 }
 
 // ---- register-resident MFMA peak probe ("to be confirmed by a register-resident MFMA micro-benchmark")

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+struct chase_hip_gemm_launch;     // include/chase_hip.h
+
 namespace chase_hip {
 
 // C = alpha*op(A)*B + beta*C, column-major, device pointers. cplx: elements are interleaved (re,im) doubles.
@@ -22,6 +24,9 @@ size_t gemm_f64_ws_need(bool cplx, char opA, int m, int n, int k, int num_cu, in
 constexpr int GEMM_F64_EWORKSPACE = -77001;
 int gemm3m_enabled();
 void gemm3m_set(int on);
+// the launches gemm_f64 makes for a product (chase_hip_gemm_plan): their count; the first max_out are written to out
+int gemm_f64_plan(bool cplx, char opA, int m, int n, int k, long lda, long ldb, bool aligned16, int tag, int num_cu, int min_rounds,
+                  chase_hip_gemm_launch* out, int max_out);
 
 int mfma_f64_peak(hipStream_t st, double* out, int blocks, int iters);
 int stream_copy(hipStream_t st, void* dst, const void* src, size_t bytes);

@@ -83,6 +83,33 @@ int chase_hip_gemm_z(chase_hip_ctx* ctx, char opA, int m, int n, int k, const do
  * k x n operand, rounded up to 64-column tiles).  A pure function of the shape (and of the 3M switch), so that the
  * decomposition and with it the summation order never depend on allocation history.  Host-only: callable without a GPU. */
 size_t chase_hip_gemm_workspace_bytes(int cplx, char opA, int m, int n, int k, int num_cu, int min_rounds);
+/* The launches chase_hip_gemm_{d,z} makes for a product, without making them (host-only: callable without a GPU).  The same
+ * decisions as the launcher, from the same code: the pieces of a 3M bulk with 4M rims and of a width in two column launches,
+ * and for each launch its tiling, work decomposition, tile order, kernel and workspace.  Arguments as chase_hip_gemm_{d,z}
+ * plus: aligned16 = A and B start on 16-byte boundaries, phase = chase_hip_ctx_set_phase's (0-3), num_cu and min_rounds as in
+ * chase_hip_gemm_workspace_bytes; the run-time switches (chase_hip_set_gemm3m, CHASE_HIP_GEMM3M_RR, CHASE_HIP_TILE_GROUP,
+ * CHASE_HIP_UNIFORM_TILES, CHASE_HIP_REAL_NARROW) apply as they do to a product.  Writes the first max_out records to out (may be
+ * NULL) and returns the number of launches (0 when m or n is 0), or CHASE_HIP_EINVAL. */
+typedef struct chase_hip_gemm_launch {
+    int row0, col0, k0;       /* the launch writes C[row0 : row0+m, col0 : col0+n] from op(A)[., k0 : k0+k] and B[k0 : k0+k, .] */
+    int m, n, k;
+    int beta_one;             /* 1: adds into C (beta = 1: the K rim of a 3M bulk, launched after it); 0: applies the caller's beta */
+    int bn_cols;              /* column stride of its output tiles (< the tile width: "uniform ragged" tiles) */
+    int narrow;               /* real 128 x 64 tile */
+    int m3;                   /* three-multiplication kernel (0: four) */
+    int ragged;               /* the last column tile skips 16-column groups */
+    int glds_ok;              /* operands copied global -> LDS directly (0: the register-staged path) */
+    int gm, gn;               /* output tiles along M and N */
+    long full_tiles;          /* tiles computed whole, one workgroup each */
+    long tail_tiles;          /* the rest, each cut into tail_sk K pieces of tail_kchunk and reduced in a fixed order */
+    int tail_sk, tail_kchunk;
+    int group_rows;           /* tile order: row panels per group */
+    int forced_split;         /* the K split is min_rounds' (every tile split), not the automatic one */
+    size_t slab_bytes;        /* workspace of the tail's partial tiles */
+    size_t plane_bytes;       /* workspace of a 3M launch's operand-sum plane, behind the slabs at a 256-byte boundary */
+} chase_hip_gemm_launch;
+int chase_hip_gemm_plan(int cplx, char opA, int m, int n, int k, long lda, long ldb, int aligned16, int phase, int num_cu,
+                        int min_rounds, chase_hip_gemm_launch* out, int max_out);
 /* 1 when complex products issued in phase 1 (chase_hip_ctx_set_phase: the Chebyshev filter) and phase 2 (the H-times-block
  * products of Rayleigh-Ritz / residuals; CHASE_HIP_GEMM3M_RR=0 keeps those on four) use the three-multiplication scheme
  * (default; CHASE_HIP_GEMM3M=0 or chase_hip_set_gemm3m(0) selects the four-multiplication kernel, the arithmetic of the
