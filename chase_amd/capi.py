@@ -67,6 +67,13 @@ _sig("chase_hip_gemm_d", c_int, c_void_p, c_char, c_int, c_int, c_int, c_double,
      c_double, c_void_p, c_long)
 _sig("chase_hip_gemm_z", c_int, c_void_p, c_char, c_int, c_int, c_int, P(c_double), c_void_p, c_long, c_void_p,
      c_long, P(c_double), c_void_p, c_long)
+_sig("chase_hip_gemm_s", c_int, c_void_p, c_char, c_int, c_int, c_int, C.c_float, c_void_p, c_long, c_void_p, c_long,
+     C.c_float, c_void_p, c_long)
+_sig("chase_hip_gemm_c", c_int, c_void_p, c_char, c_int, c_int, c_int, P(C.c_float), c_void_p, c_long, c_void_p,
+     c_long, P(C.c_float), c_void_p, c_long)
+_sig("chase_hip_convert_d2s", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_convert_s2d", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_diag_d2s", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
 _sig("chase_hip_mfma_f64_peak", c_int, c_void_p, P(c_double))
 _sig("chase_hip_gemm3m_enabled", c_int)
 _sig("chase_hip_host_lapack_warmup", c_int)
@@ -84,8 +91,14 @@ def _z2(x):
     return (c_double * 2)(x.real, x.imag)
 
 
+def _c2(x):
+    x = complex(x)
+    return (C.c_float * 2)(x.real, x.imag)
+
+
 class DeviceArray:
-    """A column-major device matrix/vector owned by a Context (fp64 or complex fp64)."""
+    """A column-major device matrix/vector owned by a Context (any numpy dtype; the kernels take fp64 / complex fp64 and,
+    for the mixed-precision filter, fp32 / complex fp32)."""
 
     def __init__(self, ctx, shape, dtype):
         self.ctx = ctx
@@ -190,6 +203,40 @@ class Context:
         else:
             check(lib.chase_hip_gemm_d(self.h, op, m, n, k, float(alpha), A, lda, B, ldb, float(beta), Cm, ldc),
                   "gemm_d")
+
+    def gemm32(self, opA, m, n, k, alpha, A, lda, B, ldb, beta, Cm, ldc, cplx):
+        """Single-precision GEMM (fp32 / complex fp32, op(A) = N only): A, B, Cm are device addresses (ints)."""
+        op = opA.encode()[0:1]
+        if cplx:
+            check(lib.chase_hip_gemm_c(self.h, op, m, n, k, _c2(alpha), A, lda, B, ldb, _c2(beta), Cm, ldc), "gemm_c")
+        else:
+            check(lib.chase_hip_gemm_s(self.h, op, m, n, k, float(alpha), A, lda, B, ldb, float(beta), Cm, ldc), "gemm_s")
+
+    def convert_d2s(self, m, n, src, ld_src, dst, ld_dst, cplx):
+        """dst (fp32) = src (fp64), round to nearest; device addresses, leading dimensions in elements."""
+        check(lib.chase_hip_convert_d2s(self.h, int(cplx), m, n, src, ld_src, dst, ld_dst), "convert_d2s")
+
+    def convert_s2d(self, m, n, src, ld_src, dst, ld_dst, cplx):
+        """dst (fp64) = src (fp32), exact."""
+        check(lib.chase_hip_convert_s2d(self.h, int(cplx), m, n, src, ld_src, dst, ld_dst), "convert_s2d")
+
+    def diag_d2s(self, n, H, ldh, Hs, ldhs, cplx):
+        """Hs[i, i] (fp32) = H[i, i] (fp64) for i < n; nothing else of Hs is written."""
+        check(lib.chase_hip_diag_d2s(self.h, int(cplx), n, H, ldh, Hs, ldhs), "diag_d2s")
+
+    def to_single(self, dA):
+        """fp32 / complex fp32 copy of an fp64 / complex fp64 DeviceArray, converted on the device."""
+        cplx = dA.dtype == np.complex128
+        out = self.empty(dA.shape, np.complex64 if cplx else np.float32)
+        self.convert_d2s(dA.shape[0], dA.shape[1], dA.ptr, dA.ld, out.ptr, out.ld, cplx)
+        return out
+
+    def to_double(self, dA):
+        """fp64 / complex fp64 copy of an fp32 / complex fp32 DeviceArray, converted on the device."""
+        cplx = dA.dtype == np.complex64
+        out = self.empty(dA.shape, np.complex128 if cplx else np.float64)
+        self.convert_s2d(dA.shape[0], dA.shape[1], dA.ptr, dA.ld, out.ptr, out.ld, cplx)
+        return out
 
     def hash64(self, ptr, m, n, ld, cplx):
         """64-bit content hash of a device matrix (chase_hip_hash64)"""

@@ -286,6 +286,42 @@ int chase_hip_lacpy(chase_hip_ctx* c, int cplx, int m, int n, const void* A, lon
     return 0;
 }
 
+int chase_hip_convert_d2s(chase_hip_ctx* c, int cplx, int m, int n, const void* src, long ld_src, void* dst, long ld_dst)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "convert_d2s: NULL ctx");
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    if (c->oplog_on) c->oplog_add("convert_d2s", m, n, 0, 0);
+    if (m < 0 || n < 0 || ld_src < m || ld_dst < m) return set_error(CHASE_HIP_EINVAL, "convert_d2s: bad shape");
+    if (m == 0 || n == 0) return 0;
+    if (!src || !dst) return set_error(CHASE_HIP_EINVAL, "convert_d2s: NULL matrix");
+    const int e = ept_of(cplx);
+    KCHK(convert_d2s(c->stream, (const double*)src, ld_src * e, (float*)dst, ld_dst * e, (long)m * e, n), "convert_d2s");
+    return 0;
+}
+
+int chase_hip_convert_s2d(chase_hip_ctx* c, int cplx, int m, int n, const void* src, long ld_src, void* dst, long ld_dst)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "convert_s2d: NULL ctx");
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    if (c->oplog_on) c->oplog_add("convert_s2d", m, n, 0, 0);
+    if (m < 0 || n < 0 || ld_src < m || ld_dst < m) return set_error(CHASE_HIP_EINVAL, "convert_s2d: bad shape");
+    if (m == 0 || n == 0) return 0;
+    if (!src || !dst) return set_error(CHASE_HIP_EINVAL, "convert_s2d: NULL matrix");
+    const int e = ept_of(cplx);
+    KCHK(convert_s2d(c->stream, (const float*)src, ld_src * e, (double*)dst, ld_dst * e, (long)m * e, n), "convert_s2d");
+    return 0;
+}
+
+int chase_hip_diag_d2s(chase_hip_ctx* c, int cplx, int n, const void* H, long ldh, void* Hs, long ldhs)
+{
+    if (!c || ((!H || !Hs) && n > 0)) return set_error(CHASE_HIP_EINVAL, "diag_d2s: NULL argument");
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    if (c->oplog_on) c->oplog_add("diag_d2s", n, 0, 0, 0);
+    if (n < 0 || ldh < n || ldhs < n) return set_error(CHASE_HIP_EINVAL, "diag_d2s: bad shape");
+    KCHK(diag_d2s(c->stream, (const double*)H, ldh, (float*)Hs, ldhs, n, ept_of(cplx)), "diag_d2s");
+    return 0;
+}
+
 int chase_hip_swap_cols(chase_hip_ctx* c, int cplx, int m, void* V, long ldv, long i, long j)
 {
     if (!c || !V) return set_error(CHASE_HIP_EINVAL, "swap_cols: NULL argument");

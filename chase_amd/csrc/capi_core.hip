@@ -254,6 +254,36 @@ int chase_hip_gemm_z(chase_hip_ctx* c, char opA, int m, int n, int k, const doub
     return c->gemm(true, opA, m, n, k, alpha, (const double*)A, lda, (const double*)B, ldb, beta, (double*)C, ldc);
 }
 
+static int gemm32(chase_hip_ctx* c, bool cplx, char opA, int m, int n, int k, const float* alpha, const float* A, long lda,
+                  const float* B, long ldb, const float* beta, float* C, long ldc)
+{
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    if (opA != 'N' && opA != 'n')
+        return set_error(CHASE_HIP_EINVAL, "gemm_s / gemm_c: opA must be 'N' (the single-precision product is the filter's)");
+    int rc = check_gemm(opA, m, n, k, A, lda, B, ldb, C, ldc);
+    if (rc || m == 0 || n == 0) return rc;
+    if (c->oplog_on) c->oplog_add(cplx ? "gemm_cN" : "gemm_sN", m, n, k, c->phase * 100);
+    int e = gemm_f32(c->stream, cplx, opA, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, c->num_cu, c->phase == 1 ? 1 : 0);
+    if (e == GEMM_F32_EOP) return set_error(CHASE_HIP_EINVAL, "gemm_s / gemm_c: opA must be 'N'");
+    if (e) return hip_fail((hipError_t)e, "gemm_f32 launch");
+    return 0;
+}
+
+int chase_hip_gemm_s(chase_hip_ctx* c, char opA, int m, int n, int k, float alpha, const float* A, long lda, const float* B,
+                     long ldb, float beta, float* C, long ldc)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "ctx == NULL");
+    return gemm32(c, false, opA, m, n, k, &alpha, A, lda, B, ldb, &beta, C, ldc);
+}
+
+int chase_hip_gemm_c(chase_hip_ctx* c, char opA, int m, int n, int k, const float alpha[2], const void* A, long lda,
+                     const void* B, long ldb, const float beta[2], void* C, long ldc)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "ctx == NULL");
+    if (!alpha || !beta) return set_error(CHASE_HIP_EINVAL, "gemm_c: NULL alpha/beta");
+    return gemm32(c, true, opA, m, n, k, alpha, (const float*)A, lda, (const float*)B, ldb, beta, (float*)C, ldc);
+}
+
 /* bytes of split-K workspace chase_hip_gemm_{d,z} uses for this shape on a device with num_cu compute units (a pure function
  * of the shape: the launcher never picks another split to fit what happens to be allocated) */
 size_t chase_hip_gemm_workspace_bytes(int cplx, char opA, int m, int n, int k, int num_cu, int min_rounds)

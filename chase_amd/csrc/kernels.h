@@ -28,6 +28,14 @@ void gemm3m_set(int on);
 int gemm_f64_plan(bool cplx, char opA, int m, int n, int k, long lda, long ldb, bool aligned16, int tag, int num_cu, int min_rounds,
                   chase_hip_gemm_launch* out, int max_out);
 
+// ---- single precision (gemm_mfma_f32.hip): the product of the mixed-precision filter.  op(A) = N only (anything else returns
+// GEMM_F32_EOP), any m, n, k and leading dimensions, operands 4-byte (real) / 8-byte (complex) aligned.  One workgroup per output
+// tile over the whole K: bitwise reproducible.  alpha / beta point to 1 (real) or 2 (complex) host floats.  tag 1: the filter's
+// own kernel symbol.
+constexpr int GEMM_F32_EOP = -77002;
+int gemm_f32(hipStream_t st, bool cplx, char opA, int m, int n, int k, const float* alpha, const float* A, long lda, const float* B,
+             long ldb, const float* beta, float* C, long ldc, int num_cu, int tag = 0);
+
 int mfma_f64_peak(hipStream_t st, double* out, int blocks, int iters);
 int stream_copy(hipStream_t st, void* dst, const void* src, size_t bytes);
 
@@ -65,6 +73,10 @@ int pack_upper(hipStream_t st, const double* A, long lda, int n, int ept, double
 int unpack_upper(hipStream_t st, double* P, int n, int ept, double* A, long lda);
 int mirror_upper(hipStream_t st, double* A, long lda, int n, int ept);
 int mirror_lower(hipStream_t st, double* A, long lda, int n, int ept, int zero_diag_imag = 1);
+// precision conversion, ms scalars per column (m * ept), leading dimensions in scalars of their own type
+int convert_d2s(hipStream_t st, const double* src, long ld_src, float* dst, long ld_dst, long ms, int ncols);   // round to nearest
+int convert_s2d(hipStream_t st, const float* src, long ld_src, double* dst, long ld_dst, long ms, int ncols);   // exact
+int diag_d2s(hipStream_t st, const double* H, long ldh, float* Hs, long ldhs, int n, int ept);                  // Hs[i,i] = (float)H[i,i]
 
 // ---- generators (gen_kernels.hip) ----
 int fill_normal(hipStream_t st, bool cplx, double* X, long ldx, int m, int n, long grow0, long gcol0, long gld,

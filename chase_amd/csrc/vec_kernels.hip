@@ -175,6 +175,48 @@ __global__ __launch_bounds__(256) void copy2d_kernel(const double* __restrict__ 
     }
 }
 
+// fp64 -> fp32 (round to nearest even) and back (exact), four scalars per lane: two 16-byte loads and one 16-byte store (or the
+// reverse) where vec says that base pointers and leading dimensions allow.  Reference: cuda/precision_conversion.cu
+__global__ __launch_bounds__(256) void convert_d2s_kernel(const double* __restrict__ src, long lds_, float* __restrict__ dst,
+                                                          long ldd, long ms, int ncols, int vec)
+{
+    for (int j = blockIdx.y; j < ncols; j += gridDim.y) {
+        const double* s = src + (long)j * lds_;
+        float* d = dst + (long)j * ldd;
+        const long n4 = vec ? (ms >> 2) : 0;
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+            const double2 a = ((const double2*)s)[2 * i], b = ((const double2*)s)[2 * i + 1];
+            ((float4*)d)[i] = make_float4((float)a.x, (float)a.y, (float)b.x, (float)b.y);
+        }
+        for (long i = 4 * n4 + (long)blockIdx.x * 256 + threadIdx.x; i < ms; i += (long)gridDim.x * 256) d[i] = (float)s[i];
+    }
+}
+__global__ __launch_bounds__(256) void convert_s2d_kernel(const float* __restrict__ src, long lds_, double* __restrict__ dst,
+                                                          long ldd, long ms, int ncols, int vec)
+{
+    for (int j = blockIdx.y; j < ncols; j += gridDim.y) {
+        const float* s = src + (long)j * lds_;
+        double* d = dst + (long)j * ldd;
+        const long n4 = vec ? (ms >> 2) : 0;
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+            const float4 a = ((const float4*)s)[i];
+            ((double2*)d)[2 * i] = make_double2((double)a.x, (double)a.y);
+            ((double2*)d)[2 * i + 1] = make_double2((double)a.z, (double)a.w);
+        }
+        for (long i = 4 * n4 + (long)blockIdx.x * 256 + threadIdx.x; i < ms; i += (long)gridDim.x * 256) d[i] = (double)s[i];
+    }
+}
+// Hs[i,i] = (float)H[i,i], both parts of a complex entry: the shadow of H follows the shifted diagonal
+__global__ void diag_d2s_kernel(const double* __restrict__ H, long ldh, float* __restrict__ Hs, long ldhs, int n, int ept)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* s = H + ((long)i * ldh + i) * ept;
+    float* d = Hs + ((long)i * ldhs + i) * ept;
+    d[0] = (float)s[0];
+    if (ept == 2) d[1] = (float)s[1];
+}
+
 // swap two columns.  Reference: chase_gpu.hpp:1003-1005 (cublasTswap), chase_cpu.hpp:820-830
 __global__ __launch_bounds__(256) void swap_kernel(double* __restrict__ a, double* __restrict__ b, long md)
 {
@@ -479,6 +521,26 @@ int copy2d(hipStream_t st, const double* src, long ld_src_d, double* dst, long l
     const int vec2 = ((md & 1) == 0) && ((ld_src_d & 1) == 0) && ((ld_dst_d & 1) == 0) &&
                      (((uintptr_t)src & 15) == 0) && (((uintptr_t)dst & 15) == 0);
     hipLaunchKernelGGL(copy2d_kernel, grid2(md, ncols), dim3(256), 0, st, src, ld_src_d, dst, ld_dst_d, md, ncols, vec2);
+    return (int)hipGetLastError();
+}
+int convert_d2s(hipStream_t st, const double* src, long ld_src, float* dst, long ld_dst, long ms, int ncols)
+{
+    if (ms <= 0 || ncols <= 0) return 0;
+    const int vec = ((ld_src & 1) == 0) && ((ld_dst & 3) == 0) && (((uintptr_t)src & 15) == 0) && (((uintptr_t)dst & 15) == 0);
+    hipLaunchKernelGGL(convert_d2s_kernel, grid2(ms, ncols), dim3(256), 0, st, src, ld_src, dst, ld_dst, ms, ncols, vec);
+    return (int)hipGetLastError();
+}
+int convert_s2d(hipStream_t st, const float* src, long ld_src, double* dst, long ld_dst, long ms, int ncols)
+{
+    if (ms <= 0 || ncols <= 0) return 0;
+    const int vec = ((ld_src & 3) == 0) && ((ld_dst & 1) == 0) && (((uintptr_t)src & 15) == 0) && (((uintptr_t)dst & 15) == 0);
+    hipLaunchKernelGGL(convert_s2d_kernel, grid2(ms, ncols), dim3(256), 0, st, src, ld_src, dst, ld_dst, ms, ncols, vec);
+    return (int)hipGetLastError();
+}
+int diag_d2s(hipStream_t st, const double* H, long ldh, float* Hs, long ldhs, int n, int ept)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(diag_d2s_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, H, ldh, Hs, ldhs, n, ept);
     return (int)hipGetLastError();
 }
 int copy_cols_indexed(hipStream_t st, const double* src, long ld_src_d, double* dst, long ld_dst_d, long md,

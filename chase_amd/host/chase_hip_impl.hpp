@@ -10,8 +10,16 @@
 //     the whole permutation in two launches (calc_degrees can issue O(n^2) swaps, algorithm.inc:181-190).
 //   * Lanczos keeps all scalars on the device (one host sync per Lanczos call instead of several per step).
 //
+//   * Mixed precision (the reference's CHASE_ENABLE_MIXED_PRECISION, chase_cpu.hpp:384-484, a compile-time option there) is a
+//     run-time switch, default off: set_mixed_precision / CHASE_HIP_MIXED_PRECISION=1.  A filter call that starts while the
+//     smallest residual of the unlocked wanted pairs is above 1e-3 runs its products in fp32 on shadow copies of H, V1 and V2.
+//     The shadow of H is converted once per solve and follows the shifted diagonal afterwards (O(N) per filter call, bitwise
+//     what converting the shifted matrix gives); only the unlocked columns are converted and copied back - locked eigenvectors
+//     are never rounded to fp32 (the reference's disableSinglePrecision(true) rounds the whole block).
+//
 // BaseT lets the same class derive from chase::ChaseBase<T> inside a ChASE checkout.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <cstdlib>
@@ -20,6 +28,7 @@
 #include <random>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/chase_hip.h"
 #include "impl_extras.hpp"
@@ -44,6 +53,7 @@ class ChaseHip : public WithOutput<BaseT>, public HipImplExtras {
 public:
     using R = Base<T>;
     static constexpr int CP = is_cplx<T>::value ? 1 : 0;
+    using ST = std::conditional_t<is_cplx<T>::value, std::complex<float>, float>;      // element of the fp32 shadows
 
     // H: N x N column-major (ldh), V1: N x (nev+nex) (ldv), ritzv: nev+nex reals.  h_on_device: H already lives in HBM
     // (it is then used in place, shifted and unshifted by the filter exactly like the reference does to its copy).
@@ -62,6 +72,7 @@ public:
         alloc((void**)&dV2_, N_ * nevex_ * sizeof(T));
         alloc((void**)&dA_, nevex_ * nevex_ * sizeof(T));
         alloc((void**)&dScal_, 4096);
+        if (const char* e = std::getenv("CHASE_HIP_MIXED_PRECISION")) mixed_ = std::atoi(e) != 0;
     }
     ~ChaseHip() override
     {
@@ -125,6 +136,7 @@ public:
         if (h_on_device_) {             // the caller's matrix lives in HBM: completed in place there (round 5)
             hip_ok(chase_hip_complete_hermitian(ctx_, CP, uplo, (int)N_, dH_, (long)ldd_h_), "complete_hermitian");
             hv_valid_ = false;
+            hs_valid_ = false;
             return;
         }
         const bool up = (uplo == 'U' || uplo == 'u');
@@ -134,10 +146,11 @@ public:
                 else    H_[i + j * ldh_] = conj_(H_[j + i * ldh_]);
             }
         h_resident_ = false;
+        hs_valid_ = false;
     }
 
     // ---- solver life cycle -------------------------------------------------------------------------------------
-    void Start() override { locked_ = 0; }
+    void Start() override { locked_ = 0; sp_active_ = false; }
 
     // reference: chase_cpu.hpp:296-327 (mt19937(1337), column-major fill) + chase_gpu.hpp:520-537 (copy, H2D)
     void initVecs(bool random) override
@@ -207,14 +220,31 @@ public:
     // true: initVecs(random) draws N(0,1) on the device like ChASEGPU; false (default): mt19937(1337) on the host,
     // bitwise the start vectors of ChASECPU (used by the parity tests)
     void set_device_rng(bool f) override { device_rng_ = f; }
-    void reset_counters() override { filter_ms_ = 0; hemm_calls_ = 0; hemm_reused_vecs_ = 0; }
+    void reset_counters() override
+    {
+        filter_ms_ = 0; hemm_calls_ = 0; hemm_reused_vecs_ = 0;
+        hemm_sp_calls_ = 0; hemm_sp_vecs_ = 0; sp_filters_ = 0;
+    }
     std::size_t hemm_calls() const override { return hemm_calls_; }
     std::size_t hemm_reused_vecs() const override { return hemm_reused_vecs_; }
+    bool set_mixed_precision(bool on) override { mixed_ = on; return true; }
+    bool mixed_precision() const override { return mixed_; }
+    std::size_t hemm_sp_calls() const override { return hemm_sp_calls_; }
+    std::size_t hemm_sp_vecs() const override { return hemm_sp_vecs_; }
+    std::size_t sp_filters() const override { return sp_filters_; }
 
-    void Shift(T c, bool = false) override
+    // The filter brackets its products with Shift(-c) ... Shift(+c, true).  Mixed precision (chase_cpu.hpp:384-445): the decision
+    // is taken here, once per filter call, from the residuals the driver left in resid_ (all max() before the first iteration).
+    void Shift(T c, bool isunshift = false) override
     {
         hv_shift_ += std::real(c);          // the cached product belongs to the unshifted matrix: (H + sI) V = H V + s V
         hip_ok(chase_hip_shift_diag(ctx_, CP, (int)N_, dH_, (long)ldd_h_, std::real(c)), "shift_diag");
+        if (isunshift) {
+            if (sp_active_) end_single_precision();
+        } else if (mixed_ && locked_ < nev_ &&
+                   *std::min_element(resid_.begin() + locked_, resid_.begin() + nev_) > (R)1e-3) {
+            begin_single_precision();
+        }
     }
 
     // V2[:, c0:c0+ncols] = alpha * H * V1[:, c0:...] + beta * V2[:, ...], c0 = locked + offset_left; then V1 <-> V2
@@ -239,6 +269,21 @@ public:
                 }
                 hip_ok(chase_hip_scale_rows(ctx_, CP, (int)N_, (int)ncols, v2, (long)N_, 0, std::real(alpha)), "scale");
                 hemm_reused_vecs_ += ncols;
+            } else if (sp_active_) {
+                if (!sp_synced_) {
+                    // the vectors enter fp32 right before the first fp32 product (the shortcut above, when it applies, has run
+                    // in fp64 by now): unlocked columns of both buffers
+                    const std::size_t sub = nevex_ - locked_;
+                    hip_ok(chase_hip_convert_d2s(ctx_, CP, (int)N_, (int)sub, dV1_ + locked_ * N_, (long)N_, sV1_ + locked_ * ld_s_,
+                                                 (long)ld_s_), "convert_d2s");
+                    hip_ok(chase_hip_convert_d2s(ctx_, CP, (int)N_, (int)sub, dV2_ + locked_ * N_, (long)N_, sV2_ + locked_ * ld_s_,
+                                                 (long)ld_s_), "convert_d2s");
+                    sp_synced_ = true;
+                    ++sp_filters_;
+                }
+                gemm32(N_, ncols, N_, alpha, sH_, ld_s_, sV1_ + c0 * ld_s_, ld_s_, beta, sV2_ + c0 * ld_s_, ld_s_);
+                ++hemm_sp_calls_;
+                hemm_sp_vecs_ += ncols;
             } else {
                 gemm('N', N_, ncols, N_, alpha, dH_, ldd_h_, dV1_ + c0 * N_, N_, beta, dV2_ + c0 * N_, N_);
                 ++hemm_calls_;
@@ -246,6 +291,7 @@ public:
         }
         hv_valid_ = false;
         std::swap(dV1_, dV2_);
+        if (sp_active_) std::swap(sV1_, sV2_);     // the shadows follow their buffers
     }
 
     // ---- QR (chase_cpu.hpp:590-776) --------------------------------------------------------------------------------
@@ -438,6 +484,48 @@ private:
         if (!h_on_device_)
             hip_ok(chase_hip_upload_matrix(ctx_, CP, (int)N_, (int)N_, H_, (long)ldh_, dH_, (long)ldd_h_), "upload H");
         h_resident_ = true;
+        hs_valid_ = false;                  // the fp32 shadow belongs to the previous matrix
+    }
+    // a qualifying Shift(-c): the fp32 shadow of the (already shifted) H.  First time after H changed: the whole matrix;
+    // afterwards the off-diagonals are still right and only the diagonal follows the shift.
+    void begin_single_precision()
+    {
+        if (!sH_) {
+            ld_s_ = (N_ + 3) & ~(std::size_t)3;            // every shadow column starts on a 16-byte boundary
+            alloc((void**)&sH_, ld_s_ * N_ * sizeof(ST));
+            alloc((void**)&sV1_, ld_s_ * nevex_ * sizeof(ST));
+            alloc((void**)&sV2_, ld_s_ * nevex_ * sizeof(ST));
+        }
+        if (!h_resident_) upload_H();
+        if (!hs_valid_) {
+            hip_ok(chase_hip_convert_d2s(ctx_, CP, (int)N_, (int)N_, dH_, (long)ldd_h_, sH_, (long)ld_s_), "convert_d2s H");
+            hs_valid_ = true;
+        } else {
+            hip_ok(chase_hip_diag_d2s(ctx_, CP, (int)N_, dH_, (long)ldd_h_, sH_, (long)ld_s_), "diag_d2s");
+        }
+        sp_active_ = true;
+        sp_synced_ = false;
+    }
+    // the unshift: the filtered (unlocked) columns return to fp64; locked columns were never touched
+    void end_single_precision()
+    {
+        if (sp_synced_)
+            hip_ok(chase_hip_convert_s2d(ctx_, CP, (int)N_, (int)(nevex_ - locked_), sV1_ + locked_ * ld_s_, (long)ld_s_,
+                                         dV1_ + locked_ * N_, (long)N_), "convert_s2d");
+        sp_active_ = false;
+        sp_synced_ = false;
+    }
+    void gemm32(std::size_t m, std::size_t n, std::size_t k, T alpha, const ST* A, std::size_t lda, const ST* B, std::size_t ldb,
+                T beta, ST* C, std::size_t ldc)
+    {
+        int rc;
+        if constexpr (is_cplx<T>::value) {
+            const float a[2] = {(float)alpha.real(), (float)alpha.imag()}, b[2] = {(float)beta.real(), (float)beta.imag()};
+            rc = chase_hip_gemm_c(ctx_, 'N', (int)m, (int)n, (int)k, a, A, (long)lda, B, (long)ldb, b, C, (long)ldc);
+        } else {
+            rc = chase_hip_gemm_s(ctx_, 'N', (int)m, (int)n, (int)k, (float)alpha, A, (long)lda, B, (long)ldb, (float)beta, C, (long)ldc);
+        }
+        hip_ok(rc, "gemm32");
     }
     void gemm(char op, std::size_t m, std::size_t n, std::size_t k, T alpha, const T* A, std::size_t lda, const T* B,
               std::size_t ldb, T beta, T* C, std::size_t ldc)
@@ -569,6 +657,10 @@ private:
     R norm_h_ = 0;                        // Lanczos upper bound of the last solve (recheck window)
     bool device_rng_ = false;
     int last_qr_variant_ = 0;
+    // mixed precision: fp32 shadows (allocated on the first qualifying filter call), their state and counters
+    bool mixed_ = false, sp_active_ = false, sp_synced_ = false, hs_valid_ = false;
+    ST *sH_ = nullptr, *sV1_ = nullptr, *sV2_ = nullptr;
+    std::size_t ld_s_ = 0, hemm_sp_calls_ = 0, hemm_sp_vecs_ = 0, sp_filters_ = 0;
 };
 
 } // namespace chase_amd

@@ -1,7 +1,10 @@
 // impl_extras.hpp — what the C entry points, the bench and the tape (tape.hpp) need from an Impl beyond the ChaseBase surface.
 // No HIP, no C ABI: includable by host-only test programs.
 #pragma once
+#include <atomic>
 #include <cstddef>
+#include <cstdio>
+#include <cstdlib>
 
 namespace chase_amd {
 
@@ -14,6 +17,12 @@ struct HipImplExtras {
     virtual std::size_t hemm_calls() const = 0;
     virtual std::size_t hemm_reused_vecs() const { return 0; }   // filter columns served from RR's cached H V (no GEMM)
     virtual std::size_t resd_rechecked() const { return 0; }     // residuals re-taken from a fresh four-product H v (on the tolerance)
+    // mixed-precision filter (single-GPU Hermitian Impl only): false = this Impl has no fp32 path and `on` was not taken
+    virtual bool set_mixed_precision(bool on) { return !on; }
+    virtual bool mixed_precision() const { return false; }
+    virtual std::size_t hemm_sp_calls() const { return 0; }      // fp32 filter products
+    virtual std::size_t hemm_sp_vecs() const { return 0; }       // columns filtered in fp32
+    virtual std::size_t sp_filters() const { return 0; }         // filter calls that ran in fp32
     virtual void set_device_rng(bool) = 0;
     virtual void reset_counters() = 0;
     virtual void* device_V1() = 0;               // current (local) vector block, pending swaps applied
@@ -37,5 +46,14 @@ struct HipImplExtras {
     virtual std::size_t replay_tolerated() const { return 0; }
     // phase marker of the profiler ranges (CHASE_HIP_ROCTX=1, roctx.hpp): nothing to implement
 };
+
+// CHASE_HIP_MIXED_PRECISION=1 reaches Impls without an fp32 filter through the environment of a whole application: said once
+inline void mixed_precision_env_ignored(const char* impl)
+{
+    static std::atomic<bool> said{false};          // (ranks of a grid may be threads of one process)
+    const char* e = std::getenv("CHASE_HIP_MIXED_PRECISION");
+    if (!e || std::atoi(e) == 0 || said.exchange(true)) return;
+    std::fprintf(stderr, "chase_hip: CHASE_HIP_MIXED_PRECISION is ignored by %s (single-GPU Hermitian solver only)\n", impl);
+}
 
 } // namespace chase_amd

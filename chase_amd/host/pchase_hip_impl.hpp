@@ -68,6 +68,7 @@ public:
     {
         if (!ctx || !grid || !H_loc || !ritzv) throw std::invalid_argument("pChaseHip: null argument");
         if (N == 0 || nevex_ == 0 || nc_ > N) throw std::invalid_argument("pChaseHip: need 0 < nev+nex <= N");
+        mixed_precision_env_ignored("the grid solvers");
         hip_ok(chase_hip_grid_info(grid, &nprow_, &npcol_, &myrow_, &mycol_), "grid_info");
         Rr_.N = Cc_.N = (long)N;
         Rr_.p = nprow_; Rr_.q = myrow_; Cc_.p = npcol_; Cc_.q = mycol_;

@@ -203,6 +203,11 @@ int chase_hip_solver_set(chase_hip_solver* s, const char* key, double v)
         else if (name == "panel_cols" && (s->pd || s->pz)) { if (s->pz) s->pz->set_panel_cols((size_t)v); else s->pd->set_panel_cols((size_t)v); }
         else if (name == "panel_rounds" && (s->pd || s->pz)) { if (s->pz) s->pz->set_panel_rounds((int)v); else s->pd->set_panel_rounds((int)v); }
         else if (name == "pipeline" && (s->pd || s->pz)) { if (s->pz) s->pz->set_pipeline(v != 0); else s->pd->set_pipeline(v != 0); }
+        else if (name == "mixed_precision") {
+            if (!s->ex->set_mixed_precision(v != 0))
+                rc = chase_hip::set_error(CHASE_HIP_EINVAL, "solver_set: mixed_precision exists on the single-GPU Hermitian solver "
+                                                            "only (grid and pseudo-Hermitian solvers filter in fp64)");
+        }
         else if (name == "reset_counters") s->ex->reset_counters();
         else rc = chase_hip::set_error(CHASE_HIP_EINVAL, "solver_set: unknown key");
     }); });
@@ -239,6 +244,10 @@ int chase_hip_solver_get(chase_hip_solver* s, const char* key, double* out)
         else if (name == "filter_ms") *out = s->ex->filter_ms();
         else if (name == "hemm_calls") *out = (double)s->ex->hemm_calls();
         else if (name == "hemm_reused_vecs") *out = (double)s->ex->hemm_reused_vecs();
+        else if (name == "mixed_precision") *out = s->ex->mixed_precision() ? 1.0 : 0.0;
+        else if (name == "hemm_sp_calls") *out = (double)s->ex->hemm_sp_calls();
+        else if (name == "hemm_sp_vecs") *out = (double)s->ex->hemm_sp_vecs();
+        else if (name == "sp_filters") *out = (double)s->ex->sp_filters();
         else if (name == "resd_rechecked") *out = (double)s->ex->resd_rechecked();
         else if (name == "tape_qr_mismatches") *out = (double)s->tape.qr_variant_mismatches;   // of the last replay
         else if (name == "tape_qr_retries") *out = (double)s->ex->forced_qr_retries();   // shifted re-factorisations, replay

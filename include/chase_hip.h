@@ -76,6 +76,16 @@ int chase_hip_gemm_d(chase_hip_ctx* ctx, char opA, int m, int n, int k, double a
                      const double* B, long ldb, double beta, double* C, long ldc);
 int chase_hip_gemm_z(chase_hip_ctx* ctx, char opA, int m, int n, int k, const double alpha[2], const void* A,
                      long lda, const void* B, long ldb, const double beta[2], void* C, long ldc);
+/* The same product in single precision (real fp32 / interleaved complex fp32) on the f32-input matrix cores: the product of the
+ * mixed-precision Chebyshev filter (replaces the cublasSgemm / cublasCgemm of the reference's CHASE_ENABLE_MIXED_PRECISION path,
+ * Impl/pchase_gpu/pchase_gpu.hpp:785-901).  opA must be 'N' (anything else: CHASE_HIP_EINVAL); any m, n, k and leading dimensions,
+ * operands aligned to their element only.  One workgroup per output tile over the whole K - no split, no atomics: results are
+ * bitwise reproducible.  beta == 0: C is not read.  Not counted by chase_hip_ctx_gemm_counters (those feed an fp64 roofline);
+ * launches in phase 1 carry a kernel symbol of their own. */
+int chase_hip_gemm_s(chase_hip_ctx* ctx, char opA, int m, int n, int k, float alpha, const float* A, long lda, const float* B,
+                     long ldb, float beta, float* C, long ldc);
+int chase_hip_gemm_c(chase_hip_ctx* ctx, char opA, int m, int n, int k, const float alpha[2], const void* A, long lda,
+                     const void* B, long ldb, const float beta[2], void* C, long ldc);
 
 /* bytes of workspace a product of this shape uses on a device with num_cu compute units (context-owned, grown on
  * demand; min_rounds as in chase_hip_ctx_set_gemm_min_rounds): the split-K slabs and - complex products while the
@@ -207,6 +217,12 @@ int chase_hip_shift_list(chase_hip_ctx* ctx, int cplx, void* H, long ldh, const 
                          int cnt, double shift);
 /* B = A (lacpy 'A').  Replaces cuda/lacpy.cu:503-835 */
 int chase_hip_lacpy(chase_hip_ctx* ctx, int cplx, int m, int n, const void* A, long lda, void* B, long ldb);
+/* Precision conversion of an m x n matrix (cplx: complex elements), leading dimensions in elements of each side's type.
+ * d2s: fp64 -> fp32, round to nearest; s2d: fp32 -> fp64, exact; diag_d2s: Hs[i,i] = (fp32) H[i,i] for i < n, nothing else of
+ * Hs is touched.  Replaces linalg/internal/cuda/precision_conversion.cu */
+int chase_hip_convert_d2s(chase_hip_ctx* ctx, int cplx, int m, int n, const void* src, long ld_src, void* dst, long ld_dst);
+int chase_hip_convert_s2d(chase_hip_ctx* ctx, int cplx, int m, int n, const void* src, long ld_src, void* dst, long ld_dst);
+int chase_hip_diag_d2s(chase_hip_ctx* ctx, int cplx, int n, const void* H, long ldh, void* Hs, long ldhs);
 /* swap columns i and j of V.  Replaces chase_gpu.hpp:1003-1005 (cublasTswap) */
 int chase_hip_swap_cols(chase_hip_ctx* ctx, int cplx, int m, void* V, long ldv, long i, long j);
 /* apply a batch of deferred Swap()s: V[:, dst[c]] <- V[:, src[c]] simultaneously; src/dst are host arrays, scratch is a
