@@ -25,12 +25,17 @@
 //   * K-contiguous tiles are stored [k-unit][row ^ k-unit] (XOR on the low 3 bits) so that the staging ds_write_b128
 //     and the fragment ds_read_b128 are both conflict-free.
 //   * complex: 4 real MFMAs per (re,im) tile step on planar fragments held in registers (interleaved in HBM/LDS); filter
-//     products: 3 real MFMAs (the "3M" scheme, see the kernel's M3 parameter).
+//     products: 3 real MFMAs (the "3M" scheme, see the kernel's M3 parameter).  The V-side operand sums br + bi of a 3M
+//     launch come from a plane that splane_kernel computes once per launch, not from v_add_f64 in the K loop (on gfx950 fp64
+//     vector adds execute on the matrix unit: ~8 cycles of the pipe each, profiles/r02_mfma_f64_issue.txt).
 //   * global -> LDS by LDS-DMA (global_load_lds_dwordx4 in its scalar-base + 32-bit lane-offset form, inline assembly: no
-//     64-bit vector address arithmetic, which on gfx950 runs on the fp64 matrix unit), 3 (complex) / 2 (real) LDS stages, the
-//     copies of the next tile hung one by one under the MFMA groups of the current one, software-pipelined fragment reads,
-//     one barrier per K step, two workgroups per CU; ragged M / unaligned operands / partial K tiles fall back to a
-//     register-staged path (global -> register -> LDS) in the same kernel.  profiles/r02_mfma_f64_issue.txt has the numbers.
+//     64-bit vector address arithmetic, which on gfx950 runs on the fp64 matrix unit), 3 (complex, narrow real) / 2 (real)
+//     LDS stages, the copies of the next tile hung one by one under the MFMA groups of the current one, one barrier per K
+//     step, two workgroups per CU.  Three K loops: complex four-product and narrow real - fragments double-buffered; 3M -
+//     fragments refilled in place, operand sums through a ring of two more LDS stages; real - one chunk's fragments at a
+//     time.  Ragged M / unaligned operands / partial K tiles fall back to a register-staged path (global -> register ->
+//     LDS) in the same kernel, which the 3M instantiations do not have (the host launches them only where every workgroup
+//     takes the LDS-DMA path).  profiles/r02_mfma_f64_issue.txt has the numbers.
 //   * XCD-aware tile order: consecutive logical tiles (same A row panel, different column panels) run on one XCD
 //     so the streamed H panel is fetched once per XCD L2.
 //   * deterministic split-K (slabs + fixed-order reduce) for the short-and-fat Gram products (k = N >> m, n).
@@ -45,21 +50,6 @@
 #include <type_traits>
 #include "../../include/chase_hip.h"
 #include "kernels.h"
-
-#ifndef CHASE_M3_PIPELINE
-#define CHASE_M3_PIPELINE 1
-#endif
-// round 6: the V-side operand sums of the 3M kernels (br + bi) come from a PRECOMPUTED plane instead of four v_add_f64 per MFMA
-// cluster (on gfx950 fp64 vector adds execute on the matrix unit: ~8 cycles of the pipe each, profiles/r02_mfma_f64_issue.txt).
-// 0 builds round 2-5's loop for comparison (scripts/dev_build_variant.sh).
-#ifndef CHASE_M3_SPLANE
-#define CHASE_M3_SPLANE 1
-#endif
-// K steps a tile of the plane-fed loop is requested ahead of its first use: 2 (three LDS stages in flight); 1 = experiment of round 6
-// (tiles one step ahead like the plane: neither faster nor slower on any device tried, profiles/r06_tile_group.txt)
-#ifndef CHASE_M3_DEPTH
-#define CHASE_M3_DEPTH 2
-#endif
 
 namespace chase_hip {
 
@@ -105,6 +95,18 @@ struct Cfg {
 // (l%8) ^ f(row): the swizzle lives on the SOURCE address); the 16-lane groups of the fragment ds_read_b128 hit 16
 // distinct 16-byte slots (conflict-free, SQ_LDS_BANK_CONFLICT = 0 measured).
 __device__ __forceinline__ int kidx(int r, int ku) { return r * 8 + (ku ^ ((r >> 1) & 7)); }
+
+// One global -> LDS copy instruction: lane l moves the 16 bytes at sbase + voff(l) to lds_dst + 16 l (lds_dst: where lane 0's go).
+// Written as inline assembly for the SGPR-base + 32-bit-lane-offset form of global_load_lds_dwordx4: the compiler's
+// intrinsic forms a 64-bit vector address first (v_lshl_add_u64), and on gfx950 64-bit vector integer adds - like v_add_f64 -
+// run on the unit that executes v_mfma_f64, so every such add is taken straight out of the matrix pipe's time
+// (profiles/r02_mfma_f64_issue.txt).  M0 = the LDS destination.  Every LDS-DMA of this file goes through here, so the
+// compiler never holds a value of its own in M0.
+__device__ __forceinline__ void glds_copy(unsigned voff, const char* sbase, const d2_t* lds_dst)
+{
+    const unsigned dst = (unsigned)(size_t)(__attribute__((address_space(3))) const void*)lds_dst;
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voff), "s"(sbase), "s"(dst) : "memory");
+}
 
 // bijective XCD remap (blocks b and b+8 share an XCD): gives each XCD a contiguous range of logical tiles
 __device__ __forceinline__ unsigned xcd_remap(unsigned b, unsigned nblk)
@@ -338,30 +340,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs p)
         }
     };
 
-    // `hook(slot)` runs after every group of MFMAs (4M: 4 MFMAs, real: TM, 3M: 3; slots 0..2 TN-1 in each case): the
+    // One 4-unit K chunk of the four-product and real kernels (the 3M kernels have their own cluster in their K loop).
+    // `hook(slot)` runs after every group of MFMAs (4M: 4 MFMAs, real: TM; slots 0..2 TN-1 in both cases): the
     // LDS-DMA loops hang the global -> LDS copies of the next tile there, one copy under each group's MFMAs
     auto no_hook = [](int) __attribute__((always_inline)) {};
     auto mfma_chunk = [&](const Frag& f, auto&& hook) __attribute__((always_inline)) {
         constexpr bool FULL = !RAGGED;                        // FULL: every 16-column group is live (no per-group branches)
-        if constexpr (CPLX && M3) {
-            double sa[TM], sb[TN];
-            #pragma unroll
-            for (int i = 0; i < TM; ++i) sa[i] = OPA_C ? f.a[i][0] - f.a[i][1] : f.a[i][0] + f.a[i][1];
-            #pragma unroll
-            for (int j = 0; j < TN; ++j) sb[j] = f.b[j].x + f.b[j].y;
-            #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                #pragma unroll
-                for (int i = 0; i < TM; ++i) {
-                    if (FULL || j < jv) {
-                        acc[0][j][i] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.b[j].x, f.a[i][0], acc[0][j][i], 0, 0, 0);
-                        acc[1][j][i] = __builtin_amdgcn_mfma_f64_16x16x4f64(f.b[j].y, f.a[i][1], acc[1][j][i], 0, 0, 0);
-                        acc[2][j][i] = __builtin_amdgcn_mfma_f64_16x16x4f64(sb[j], sa[i], acc[2][j][i], 0, 0, 0);
-                    }
-                    hook(TM * j + i);
-                }
-            }
-        } else if constexpr (CPLX) {
+        if constexpr (CPLX) {
             // op=N: (ar + i ai)(br + i bi): re = br ar - bi ai, im = bi ar + br ai
             // op=C: (ar - i ai)(br + i bi): re = br ar + bi ai, im = bi ar - br ai      -> one negated B value per tile
             double nb[TN];
@@ -402,9 +387,9 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs p)
         }
     };
 
-    // whole K step from one LDS stage (register-staged fallback path)
+    // whole K step from one LDS stage (register-staged fallback path, the real LDS-DMA loop)
     auto compute = [&](int stage, auto&& hook) __attribute__((always_inline)) {
-        if constexpr (C_::PIPELINED && !M3) {
+        if constexpr (C_::PIPELINED) {
             Frag f0, f1;
             read_chunk(stage, 0, f0);
             read_chunk(stage, 1, f1);
@@ -442,20 +427,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs p)
             constexpr int NA = C_::A_GLDS / 4, NB = C_::B_GLDS / 4;
             const char* sa[NA];                                 // uniform
             unsigned va[NA];                                    // per lane, bytes
-            // diagnostic builds (timing only, results wrong on purpose; scripts/dev_build_variant.sh): every workgroup streams
-            // the SAME A row panel / the same B column panel, so that operand is served by the L2s - what would a launch gain if
-            // its re-reads never left the L2?  (profiles/r04_traffic_upper_bound.txt)
-#ifdef CHASE_DIAG_SAME_A
-            const int row0_src = 0;
-#else
-            const int row0_src = row0;
-#endif
-#ifdef CHASE_DIAG_SAME_B
-            const int col0_src = 0;
-#else
-            const int col0_src = col0;
-#endif
-            const char* sb = (const char*)(p.B + ((long)col0_src * p.ldb + kbeg) * EPT);
+            const char* sb = (const char*)(p.B + ((long)col0 * p.ldb + kbeg) * EPT);
             unsigned vb[NB];
             #pragma unroll
             for (int u = 0; u < NA; ++u) {
@@ -463,13 +435,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs p)
                 if constexpr (!OPA_C) {
                     // [k][unit] image: complex 128 units per k row (two instructions), real 64 units (one)
                     const int kk = CPLX ? (t >> 1) : t, half = CPLX ? (t & 1) : 0;
-                    sa[u] = (const char*)(p.A + ((long)(kbeg + kk) * p.lda + row0_src) * EPT + (long)half * 128);
+                    sa[u] = (const char*)(p.A + ((long)(kbeg + kk) * p.lda + row0) * EPT + (long)half * 128);
                     va[u] = (unsigned)lane * 16u;
                 } else {
                     // row r = 8 t + lane / 8: the 8 t rows go into the uniform base; the swizzle (r >> 1) & 7 = (4 t + lane / 16) & 7
                     // depends on t through its parity only, so the lane offsets of copies u and u + 2 are the same register
                     const int rl = lane >> 3, ku = (lane & 7) ^ ((4 * t + (lane >> 4)) & 7);
-                    sa[u] = (const char*)(p.A + ((long)(row0_src + 8 * t) * p.lda + kbeg) * EPT);
+                    sa[u] = (const char*)(p.A + ((long)(row0 + 8 * t) * p.lda + kbeg) * EPT);
                     va[u] = (unsigned)(((long)rl * p.lda + ku * KPU) * EPT * 8);
                 }
             }
@@ -482,42 +454,35 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs p)
             }
             const long stepA = (OPA_C ? (long)BK * EPT : (long)BK * p.lda * EPT) * 8;
             constexpr long stepB = (long)BK * EPT * 8;
+            auto next_stage = [](int st) { return (st + 1 == C_::STAGES) ? 0 : st + 1; };
             int st_issue = 0;                                   // stage the next issue() fills
-            // One global -> LDS copy instruction (64 lanes x 16 B) of the tile being requested.  Written as inline assembly
-            // for the SGPR-base + 32-bit-lane-offset form of global_load_lds_dwordx4: the compiler's intrinsic forms a
-            // 64-bit vector address first (v_lshl_add_u64), and on gfx950 64-bit vector integer adds - like v_add_f64 - run on
-            // the unit that executes v_mfma_f64, so every such add is taken straight out of the matrix pipe's time
-            // (profiles/r02_mfma_f64_issue.txt).  M0 = LDS destination of lane 0.  Every LDS-DMA of this kernel goes through
-            // here, so the compiler never holds a value of its own in M0.
+            // One copy instruction (glds_copy) of the tile being requested: copy u of this wave's NA + NB, into `stage`
             auto issue_one = [&](int u, int stage) __attribute__((always_inline)) {
-                // (the plane-fed 3M kernels keep all A stages together, then all B stages: one LDS base register per fragment
+                // (the 3M kernels keep all A stages together, then all B stages: one LDS base register per fragment
                 // pattern reaches every stage through the 16-bit immediate offset of ds_read)
-                constexpr bool SPLIT = CPLX && M3 && CHASE_M3_SPLANE;
+                constexpr bool SPLIT = CPLX && M3;
                 d2_t* sA = SPLIT ? lds + stage * C_::A_UNITS : lds + stage * C_::STAGE_UNITS;
                 d2_t* sB = SPLIT ? lds + C_::STAGES * C_::A_UNITS + stage * C_::B_UNITS : sA + C_::A_UNITS;
                 if (u < NA) {
-                    const unsigned dst = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(sA + (wv * NA + u) * 64);
-                    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                                 :: "v"(va[u]), "s"(sa[u]), "s"(dst) : "memory");
+                    glds_copy(va[u], sa[u], sA + (wv * NA + u) * 64);
                     sa[u] += stepA;
                 } else {
                     const int ub = u - NA;
-                    const unsigned dst = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(sB + (wv * NB + ub) * 64);
-                    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                                 :: "v"(vb[ub]), "s"(sb), "s"(dst) : "memory");
+                    glds_copy(vb[ub], sb, sB + (wv * NB + ub) * 64);
                 }
                 if (u == NA + NB - 1) sb += stepB;
             };
             auto issue = [&]() __attribute__((always_inline)) {
                 #pragma unroll
                 for (int u = 0; u < NA + NB; ++u) issue_one(u, st_issue);
-                st_issue = (st_issue + 1 == C_::STAGES) ? 0 : st_issue + 1;
+                st_issue = next_stage(st_issue);
             };
             if constexpr (C_::PIPELINED && !M3) {
-                // Software pipeline (complex four-product kernel and the narrow real kernel): all STAGES tiles are requested up front; each K step multiplies chunk 0 from registers
-                // while chunk 1's fragments stream in from LDS, and the barrier that publishes tile kt+1 sits BETWEEN the two
-                // MFMA clusters, so chunk 0 of tile kt+1 is fetched under chunk 1's MFMAs and the stage of tile kt is refilled
-                // (tile kt+STAGES) as soon as its last fragment has been read: no MFMA ever waits for an LDS read.
+                // Software pipeline (complex four-product kernel and the narrow real kernel): all STAGES tiles are requested up
+                // front; each K step multiplies chunk 0 from registers while chunk 1's fragments stream in from LDS, and the
+                // barrier that publishes tile kt+1 sits BETWEEN the two MFMA clusters, so chunk 0 of tile kt+1 is fetched under
+                // chunk 1's MFMAs and the stage of tile kt is refilled (tile kt+STAGES) as soon as its last fragment has been
+                // read: no MFMA ever waits for an LDS read.
                 constexpr int G = C_::GLDS_PER_WAVE;
                 const int npre = min(nfull, C_::STAGES);
                 for (int t = 0; t < npre; ++t) issue();
@@ -533,7 +498,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs p)
                 // one K step on the tile in stage st (not the last one); `fill`: tile kt+STAGES exists and goes into stage st,
                 // one copy after every fourth MFMA of the second cluster
                 auto kstep = [&](int kt, int st, auto fill_c) __attribute__((always_inline)) {
-                    const int stn = (st + 1 == C_::STAGES) ? 0 : st + 1;
+                    const int stn = next_stage(st);
                     read_chunk(st, 1, fB);
                     __builtin_amdgcn_sched_barrier(0);
                     mfma_chunk(fA, no_hook);
@@ -559,28 +524,29 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs p)
                 };
                 static_assert(2 * TN >= NA + NB, "one copy per MFMA group of the cluster");
                 int st = 0, kt = 0;
-                for (; kt + C_::STAGES < nfull; ++kt) { kstep(kt, st, yes); st = (st + 1 == C_::STAGES) ? 0 : st + 1; }
-                for (; kt + 1 < nfull; ++kt)          { kstep(kt, st, no);  st = (st + 1 == C_::STAGES) ? 0 : st + 1; }
+                for (; kt + C_::STAGES < nfull; ++kt) { kstep(kt, st, yes); st = next_stage(st); }
+                for (; kt + 1 < nfull; ++kt)          { kstep(kt, st, no);  st = next_stage(st); }
                 read_chunk(st, 1, fB);                                         // last tile: nothing to publish or prefetch
                 __builtin_amdgcn_sched_barrier(0);
                 mfma_chunk(fA, no_hook);
                 __builtin_amdgcn_sched_barrier(0);
                 mfma_chunk(fB, no_hook);
-            } else if constexpr (CPLX && M3 && CHASE_M3_SPLANE) {
-                // 3M software pipeline, round 6: V-side operand sums from the precomputed plane p.S.
+            } else if constexpr (CPLX && M3) {
+                // 3M software pipeline: V-side operand sums from the precomputed plane p.S.  192 accumulator registers leave
+                // no room for a second set of fragments, so every fragment is refilled in place behind its last reader.
                 //   * LDS: the three 24 KB stages + a RING OF TWO 4 KB stages for the plane = 80 KB (two workgroups still fit
                 //     the CU's 160 KB).  S(kt) lives in ring stage kt & 1, image [4 k pairs][64 columns][2] doubles, brought in by ONE
                 //     more global -> LDS copy per wave and K step (1 KB of the 4 KB block each, linear: the plane is stored in
                 //     this image).  S(kt + 2) is requested right after the mid-step barrier of step kt (all reads of S(kt)
                 //     have completed by then), BEFORE the copies of tile kt + 3, so that the counted vmcnt of the next step
-                //     covers it: the waits are the ones of rounds 2-5.
+                //     covers it: the waits count G copies in flight like the four-product loop's.
                 //   * MFMA order inside a cluster: row tile by row tile (i outer).  An A fragment is then REFILLED IN PLACE
-                //     after its 12 MFMAs like the B fragments after theirs (no second A buffer: 8 registers, which the four
-                //     prefetched sum fragments take); every refill is issued >= 9 MFMAs (576 cycles) before its first reader.
+                //     after its 12 MFMAs like the B fragments after theirs (no second A buffer: its 8 registers hold the four
+                //     prefetched sum fragments); every refill is issued >= 9 MFMAs (576 cycles) before its first reader.
                 //   * per cluster: 24 MFMAs, 2 v_add_f64 (the H-side sums ar +- ai, per wave private rows: they cannot be
-                //     shared) instead of 6, 6 ds_read_b128 + 4 ds_read_b64.
-                // Results are bitwise those of rounds 2-5: the plane holds the same IEEE sums br + bi, the accumulators are
-                // independent of each other, so the MFMA order does not matter.
+                //     shared), 6 ds_read_b128 + 4 ds_read_b64.
+                // The plane holds the IEEE sums br + bi that an add in the loop would give, and the accumulators are independent
+                // of each other, so neither the plane nor the MFMA order changes a bit of the result.
                 constexpr int G = C_::GLDS_PER_WAVE;
                 constexpr int S_UNITS = 256;                                   // 16-byte units per ring stage (4 KB)
                 d2_t* const sring = lds + C_::STAGES * C_::STAGE_UNITS;
@@ -588,14 +554,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs p)
                 const unsigned vs = (unsigned)lane * 16u;
                 int s_issue = 0;                                               // ring stage the next plane copy fills
                 auto issue_s = [&]() __attribute__((always_inline)) {
-                    const unsigned dst = (unsigned)(size_t)(__attribute__((address_space(3))) void*)(sring + s_issue * S_UNITS + wv * 64);
-                    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                                 :: "v"(vs), "s"(ssrc), "s"(dst) : "memory");
+                    glds_copy(vs, ssrc, sring + s_issue * S_UNITS + wv * 64);
                     ssrc += 4096;
                     s_issue ^= 1;
                 };
-                constexpr bool DEPTH1 = (CHASE_M3_DEPTH == 1);
-                const int npre = min(nfull, DEPTH1 ? 2 : C_::STAGES);
+                const int npre = min(nfull, C_::STAGES);
                 issue_s(); issue();                                            // S(0), T(0)
                 if (npre > 1) { issue_s(); issue(); }                          // S(1), T(1)
                 if (npre > 2) issue();                                         // T(2)
@@ -640,13 +603,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs p)
                     constexpr bool fill_s = decltype(fill_s_c)::value;
                     #pragma unroll
                     for (int i = 0; i < TM; ++i) {
-#ifdef CHASE_DIAG_NO_SA
-                        // diagnostic build (timing only, results wrong on purpose): what would a launch gain if the H-side operand sums
-                        // cost nothing (profiles/r06_dropped_with_data.txt)
-                        const double sa = aC[i].x;
-#else
                         const double sa = OPA_C ? aC[i].x - aC[i].y : aC[i].x + aC[i].y;
-#endif
                         #pragma unroll
                         for (int j = 0; j < TN; ++j) {
                             if (!RAGGED || j < jv) {                           // ragged tile: groups past n carry no MFMAs
@@ -681,11 +638,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs p)
                 // one K step on the tile in stage st; fill_t: tile kt+STAGES exists and goes into stage st; fill_s: tile kt+2
                 // exists, its plane block goes into the ring stage this step has just finished reading
                 auto kstep = [&](int kt, int st, auto fill_t_c, auto fill_s_c) __attribute__((always_inline)) {
-                    const int stn = (st + 1 == C_::STAGES) ? 0 : st + 1;
+                    const int stn = next_stage(st);
                     cluster(st, 1, yes, no, no);                               // chunk 0 of tile kt, prefetching its chunk 1
                     // my reads of stage st and of its ring stage are complete, my copies of tile kt+1 and of its plane block
                     // have landed; tile kt+2 (requested one step ago) may stay in flight
-                    if (!DEPTH1 && (decltype(fill_t_c)::value || kt + 2 < nfull))
+                    if (decltype(fill_t_c)::value || kt + 2 < nfull)
                         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(G) : "memory");
                     else
                         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -693,139 +650,31 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs p)
                     asm volatile("" ::: "memory");
                     soff ^= 4096u;                                             // the other ring stage: tile kt+1's sums
                     __builtin_amdgcn_sched_barrier(0);
-                    // (DEPTH1: the tile requested here is kt+2, into the stage BEHIND st, free since the previous step)
-                    cluster(stn, 0, yes, fill_t_c, fill_s_c, DEPTH1 ? (st == 0 ? C_::STAGES - 1 : st - 1) : st);   // chunk 1 of tile kt (+ the copies)
+                    cluster(stn, 0, yes, fill_t_c, fill_s_c, st);              // chunk 1 of tile kt (+ the copies)
                 };
                 int kt = 0;
                 // steady state, three K steps per trip: the stage indices are compile-time constants, so every LDS address is a
-                // loop-invariant register plus an immediate offset (the ring stage of the sums: one xor per K step)
-                constexpr int AHEAD = DEPTH1 ? 2 : C_::STAGES;                 // the tile a step requests: kt + AHEAD
+                // loop-invariant register plus an immediate offset (the ring stage of the sums: one xor per K step).  The four
+                // RAGGED instantiations park a few VGPRs in scratch across the K loops (op = C five, op = N two: stored before
+                // the loops, loaded after them); tests/test_kernel_resources.py checks that no scratch access sits inside a loop
+                // and that the whole-tile instantiations have none.
                 if constexpr (C_::STAGES == 3) {
-                    for (; kt + 2 + AHEAD < nfull; kt += 3) {
+                    for (; kt + 2 + C_::STAGES < nfull; kt += 3) {
                         kstep(kt, 0, yes, yes);
                         kstep(kt + 1, 1, yes, yes);
                         kstep(kt + 2, 2, yes, yes);
                     }
                 }
                 int st = 0;                                                    // kt is a multiple of STAGES here
-                for (; kt + AHEAD < nfull; ++kt) { kstep(kt, st, yes, yes); st = (st + 1 == C_::STAGES) ? 0 : st + 1; }
-                if (!DEPTH1 && kt + 2 < nfull)        { kstep(kt, st, no, yes);  st = (st + 1 == C_::STAGES) ? 0 : st + 1; ++kt; }
-                for (; kt + 1 < nfull; ++kt)          { kstep(kt, st, no, no);   st = (st + 1 == C_::STAGES) ? 0 : st + 1; }
+                for (; kt + C_::STAGES < nfull; ++kt) { kstep(kt, st, yes, yes); st = next_stage(st); }
+                if (kt + 2 < nfull)                   { kstep(kt, st, no, yes);  st = next_stage(st); ++kt; }
+                for (; kt + 1 < nfull; ++kt)          { kstep(kt, st, no, no);   st = next_stage(st); }
                 cluster(st, 1, yes, no, no);                                   // last tile: nothing to publish or prefetch after it
                 __builtin_amdgcn_sched_barrier(0);
                 cluster(st, 1, no, no, no);
-            } else if constexpr (CPLX && M3 && CHASE_M3_PIPELINE) {
-                // (rounds 2-5, kept for comparison builds: -DCHASE_M3_SPLANE=0)
-                // 3M software pipeline.  192 accumulator registers leave no room for a second set of fragments, so only
-                // the A fragments (8 registers) are double-buffered; each B fragment is REFILLED IN PLACE with the next
-                // chunk's data right after the six MFMAs that were its last readers, i.e. 18 MFMAs (>1000 cycles) before
-                // it is needed again.  The barrier that publishes tile kt+1 sits between the two MFMA clusters like in the
-                // four-product loop above, and the stage of tile kt is refilled as soon as its last fragment has been read.
-                constexpr int G = C_::GLDS_PER_WAVE;
-                const int npre = min(nfull, C_::STAGES);
-                for (int t = 0; t < npre; ++t) issue();
-                if (npre == 3)      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * G) : "memory");
-                else if (npre == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G) : "memory");
-                else                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-                auto ld_a = [&](int stage, int ch, d2_t (&a)[TM]) __attribute__((always_inline)) {
-                    const d2_t* sA = lds + stage * C_::STAGE_UNITS;
-                    const int ku = 4 * ch + q;
-                    #pragma unroll
-                    for (int i = 0; i < TM; ++i) {
-                        const int r = wrow + 16 * i + c16;
-                        if constexpr (OPA_C) a[i] = sA[kidx(r, ku)];
-                        else                 a[i] = sA[ku * UM + r];
-                    }
-                };
-                auto ld_b = [&](int stage, int ch, int j) __attribute__((always_inline)) -> d2_t {
-                    const d2_t* sB = lds + stage * C_::STAGE_UNITS + C_::A_UNITS;
-                    return sB[kidx(wcol + 16 * j + c16, 4 * ch + q)];
-                };
-                d2_t aC[TM], aN[TM], bF[TN];
-                ld_a(0, 0, aC);
-                #pragma unroll
-                for (int j = 0; j < TN; ++j) bF[j] = ld_b(0, 0, j);
-                // One MFMA cluster on (aC, bF) while the fragments of (nstage, nch) stream in; `more`: there is a next chunk.
-                // `fill`: the cluster also requests tile kt+STAGES: its six global -> LDS copies are spread over the cluster,
-                // one after every third MFMA, so that each copy's issue slot lies under an MFMA in flight (issued as one
-                // block after the barrier they cost 4 % of the loop, profiles/r02_mfma_f64_issue.txt).
-                auto cluster = [&](int nstage, int nch, auto more_c, auto fill_c, int fstage = 0) __attribute__((always_inline)) {
-                    constexpr bool more = decltype(more_c)::value;
-                    constexpr bool fill = decltype(fill_c)::value;
-                    double sa[TM];
-                    #pragma unroll
-                    for (int i = 0; i < TM; ++i) sa[i] = OPA_C ? aC[i].x - aC[i].y : aC[i].x + aC[i].y;
-                    if (more) ld_a(nstage, nch, aN);
-                    #pragma unroll
-                    for (int j = 0; j < TN; ++j) {
-                        const double sb = bF[j].x + bF[j].y;
-                        #pragma unroll
-                        for (int i = 0; i < TM; ++i) {
-                            if (!RAGGED || j < jv) {                           // ragged tile: groups past n carry no MFMAs
-                                acc[0][j][i] = __builtin_amdgcn_mfma_f64_16x16x4f64(bF[j].x, aC[i].x, acc[0][j][i], 0, 0, 0);
-                                acc[1][j][i] = __builtin_amdgcn_mfma_f64_16x16x4f64(bF[j].y, aC[i].y, acc[1][j][i], 0, 0, 0);
-                                acc[2][j][i] = __builtin_amdgcn_mfma_f64_16x16x4f64(sb, sa[i], acc[2][j][i], 0, 0, 0);
-                            }
-                            if (fill && (TM * j + i) < NA + NB) {
-                                __builtin_amdgcn_sched_barrier(0);
-                                issue_one(TM * j + i, fstage);
-                                __builtin_amdgcn_sched_barrier(0);
-                            }
-                        }
-                        if (more) bF[j] = ld_b(nstage, nch, j);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    #pragma unroll
-                    for (int i = 0; i < TM; ++i) aC[i] = aN[i];
-                };
-                static_assert(TM * TN >= NA + NB, "one copy per (j, i) slot of the cluster");
-                constexpr std::true_type yes{};
-                constexpr std::false_type no{};
-                // one K step on the tile in stage st; `fill`: tile kt+STAGES exists and goes into stage st
-                auto kstep = [&](int kt, int st, auto fill_c) __attribute__((always_inline)) {
-                    const int stn = (st + 1 == C_::STAGES) ? 0 : st + 1;
-                    cluster(st, 1, yes, no);                                   // chunk 0 of tile kt, prefetching its chunk 1
-                    // my reads of stage st are complete and my copies of tile kt+1 have landed; tile kt+2 (requested one
-                    // step ago) may stay in flight
-                    if (C_::STAGES > 2 && (decltype(fill_c)::value || kt + 2 < nfull))
-                        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(G) : "memory");
-                    else
-                        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                    __builtin_amdgcn_s_barrier();
-                    asm volatile("" ::: "memory");
-                    __builtin_amdgcn_sched_barrier(0);
-                    cluster(stn, 0, yes, fill_c, st);                          // chunk 1 of tile kt (+ the copies of tile kt+STAGES)
-                };
-                int kt = 0;
-                // steady state, three K steps per trip: the stage indices are compile-time constants, so every LDS address is a
-                // loop-invariant register plus an immediate offset (no address arithmetic in the loop).  In the two ragged op = C
-                // instantiations this form parks ONE VGPR in scratch across the K loop (one store before the loops, one load after
-                // them - tests/test_kernel_resources.py checks that no scratch access sits inside a loop); the form without the
-                // unrolled loop needs no scratch but runs all-ragged launches 3 % slower (profiles/r04_ragged_c_compare.txt), so the
-                // unrolled form stays.  -DCHASE_NO_RAGGED_C_UNROLL builds the comparison.
-#ifdef CHASE_NO_RAGGED_C_UNROLL
-                constexpr bool unroll3 = (C_::STAGES == 3) && !(RAGGED && OPA_C);
-#else
-                constexpr bool unroll3 = (C_::STAGES == 3);
-#endif
-                if constexpr (unroll3) {
-                    for (; kt + 2 + C_::STAGES < nfull; kt += 3) {
-                        kstep(kt, 0, yes);
-                        kstep(kt + 1, 1, yes);
-                        kstep(kt + 2, 2, yes);
-                    }
-                }
-                int st = 0;                                                    // kt is a multiple of STAGES here
-                for (; kt + C_::STAGES < nfull; ++kt) { kstep(kt, st, yes); st = (st + 1 == C_::STAGES) ? 0 : st + 1; }
-                for (; kt + 1 < nfull; ++kt)          { kstep(kt, st, no);  st = (st + 1 == C_::STAGES) ? 0 : st + 1; }
-                cluster(st, 1, yes, no);                                       // last tile: nothing to publish or prefetch after it
-                __builtin_amdgcn_sched_barrier(0);
-                cluster(st, 1, no, no);
             } else {
                 // real (80 fragment registers next to 128 accumulator registers) cannot double-buffer fragments: one barrier
-                // per K step, each chunk's fragments fetched right before its MFMAs (also the 3M loop without pipelining)
+                // per K step, each chunk's fragments fetched right before its MFMAs
                 constexpr int DEPTH = C_::STAGES - 1;
                 issue();
                 if (DEPTH > 1 && nfull > 1) issue();
@@ -847,7 +696,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f64_kernel(GemmArgs p)
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     });
-                    st_comp = (st_comp + 1 == C_::STAGES) ? 0 : st_comp + 1;
+                    st_comp = next_stage(st_comp);
                 };
                 static_assert(2 * TN >= NA + NB, "one copy per MFMA group of the cluster");
                 int kt = 0;
@@ -1183,7 +1032,7 @@ static PartDecision decide_part(int m, int n, int k, long lda, long ldb, bool al
     if (bn_cols <= 0 || bn_cols > C_::BN) bn_cols = C_::BN;
     d.bn_cols = bn_cols;
     d.gm = (m + C_::BM - 1) / C_::BM; d.gn = (n + bn_cols - 1) / bn_cols;
-    // Row panels per group of the tile order (tile_coords): 2; FOUR for launches of many rounds with many column tiles (round 6).
+    // Row panels per group of the tile order (tile_coords): 2; FOUR for launches of many rounds with many column tiles.
     // With the plane-fed 3M loop the workgroups that share panels stay in step, so a 4 x 16 patch of tiles per XCD (256 KB of
     // unique operands per K step instead of 416 KB) really is served by the L2: 0.89 instead of 1.31 TB through the fabric for
     // the full-width config-4 launch, the same time on a device that holds its clock (873 vs 875 ms) and 2 % less on one that
@@ -1211,8 +1060,8 @@ static PartDecision decide_part(int m, int n, int k, long lda, long ldb, bool al
     // k = 0 (C = beta C, nothing to multiply) stays on four: the operand-sum plane of an empty K range would be a launch of
     // zero workgroups.  Its plane sits in the workspace, so without one: four products.
     d.m3 = CPLX && allow3m && gemm3m_enabled() != 0 && d.glds_ok && k > 0 && (m % C_::BM == 0) && (k % C_::BK == 0) &&
-           (d.kchunk % C_::BK == 0) && (!CHASE_M3_SPLANE || have_ws);
-    d.plane_bytes = (d.m3 && CHASE_M3_SPLANE) ? splane_bytes(n, k, bn_cols) : 0;
+           (d.kchunk % C_::BK == 0) && have_ws;
+    d.plane_bytes = d.m3 ? splane_bytes(n, k, bn_cols) : 0;
     return d;
 }
 
@@ -1238,9 +1087,6 @@ static int launch_gemm_part(hipStream_t st, int m, int n, int k, const double* a
     a.glds_ok = d.glds_ok;
     const unsigned grid = (unsigned)(full + tail * sk);
     const size_t lds_bytes = (size_t)C_::STAGES * C_::STAGE_UNITS * sizeof(d2_t);
-    // 3M kernels: + the ring of two 4 KB stages of the operand-sum plane (80 KB: two workgroups per CU still fit)
-    const size_t lds_bytes3 = lds_bytes + (CHASE_M3_SPLANE ? 2 * 4096 : 0);
-    const bool ragged = d.ragged;
     // the dynamic-LDS limit is a per-device function attribute: one flag per device (setting it twice is harmless, so a
     // relaxed atomic is enough for concurrent first calls)
     const int dev = (li.device >= 0 && li.device < MAX_DEVICES) ? li.device : 0;
@@ -1250,17 +1096,17 @@ static int launch_gemm_part(hipStream_t st, int m, int n, int k, const double* a
         (void)hipFuncSetAttribute((const void*)gemm_f64_kernel<CPLX, OPA_C, TAG, true, false, NARROW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         attr_set[dev].store(true, std::memory_order_relaxed);
     }
-    constexpr bool CAN3M = CPLX;
-    const bool ok3m = d.m3;
     a.S = nullptr; a.s_nkt = 0;
-    if constexpr (CAN3M) {
+    if constexpr (CPLX) {                                               // d.m3 implies CPLX: no 3M kernel exists for real types
+        // 3M kernels: + the ring of two 4 KB stages of the operand-sum plane (80 KB: two workgroups per CU still fit)
+        const size_t lds_bytes3 = lds_bytes + 2 * 4096;
         static std::atomic<bool> attr3[MAX_DEVICES];
         if (!attr3[dev].load(std::memory_order_relaxed)) {
-            (void)hipFuncSetAttribute((const void*)gemm_f64_kernel<CPLX, OPA_C, TAG, false, CAN3M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes3);
-            (void)hipFuncSetAttribute((const void*)gemm_f64_kernel<CPLX, OPA_C, TAG, true, CAN3M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes3);
+            (void)hipFuncSetAttribute((const void*)gemm_f64_kernel<CPLX, OPA_C, TAG, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes3);
+            (void)hipFuncSetAttribute((const void*)gemm_f64_kernel<CPLX, OPA_C, TAG, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes3);
             attr3[dev].store(true, std::memory_order_relaxed);
         }
-        if (ok3m && CHASE_M3_SPLANE) {
+        if (d.m3) {
             // the operand-sum plane sits behind the slabs in the caller's workspace (gemm_f64_ws_need counts it); written on the
             // same stream right before the product
             const size_t off = (d.pl.ws_bytes + 255) & ~(size_t)255;
@@ -1269,22 +1115,20 @@ static int launch_gemm_part(hipStream_t st, int m, int n, int k, const double* a
             hipLaunchKernelGGL(splane_kernel, dim3((unsigned)((k + 63) / 64), (unsigned)a.gn), dim3(256), 0, st, B, ldb, n, k,
                                d.bn_cols, k / C_::BK, S);
             a.S = S; a.s_nkt = k / C_::BK;
-        }
-        if (ok3m) {
-            if (ragged) hipLaunchKernelGGL((gemm_f64_kernel<CPLX, OPA_C, TAG, true, CAN3M>), dim3(grid), dim3(256), lds_bytes3, st, a);
-            else        hipLaunchKernelGGL((gemm_f64_kernel<CPLX, OPA_C, TAG, false, CAN3M>), dim3(grid), dim3(256), lds_bytes3, st, a);
+            if (d.ragged) hipLaunchKernelGGL((gemm_f64_kernel<CPLX, OPA_C, TAG, true, true>), dim3(grid), dim3(256), lds_bytes3, st, a);
+            else          hipLaunchKernelGGL((gemm_f64_kernel<CPLX, OPA_C, TAG, false, true>), dim3(grid), dim3(256), lds_bytes3, st, a);
         }
     }
-    if (!(CAN3M && ok3m)) {
-        if (ragged) hipLaunchKernelGGL((gemm_f64_kernel<CPLX, OPA_C, TAG, true, false, NARROW>), dim3(grid), dim3(256), lds_bytes, st, a);
-        else        hipLaunchKernelGGL((gemm_f64_kernel<CPLX, OPA_C, TAG, false, false, NARROW>), dim3(grid), dim3(256), lds_bytes, st, a);
+    if (!d.m3) {
+        if (d.ragged) hipLaunchKernelGGL((gemm_f64_kernel<CPLX, OPA_C, TAG, true, false, NARROW>), dim3(grid), dim3(256), lds_bytes, st, a);
+        else          hipLaunchKernelGGL((gemm_f64_kernel<CPLX, OPA_C, TAG, false, false, NARROW>), dim3(grid), dim3(256), lds_bytes, st, a);
     }
     if (tail > 0) {
         hipLaunchKernelGGL((tail_reduce_kernel<CPLX, C_::BM, C_::BN>), dim3((unsigned)tail * TAIL_PARTS), dim3(256), 0, st, ws,
                            (int)full, sk, a.gn, m, n, C, ldc, a.alpha_re, a.alpha_im, a.beta_re, a.beta_im, a.group_rows, a.bn_cols);
     }
     // flops the matrix cores execute for this product: the reference's model 2*F*m*n*k (F = 4 complex), 3/4 of it in 3M
-    if (li.exec_flops) *li.exec_flops += 2.0 * (CPLX ? 4.0 : 1.0) * m * (double)n * k * ((CAN3M && ok3m) ? 0.75 : 1.0);
+    if (li.exec_flops) *li.exec_flops += 2.0 * (CPLX ? 4.0 : 1.0) * m * (double)n * k * (d.m3 ? 0.75 : 1.0);
     return (int)hipGetLastError();
 }
 
@@ -1399,7 +1243,7 @@ static size_t ws_need(int m, int n, int k, int num_cu, int min_rounds)
             b = plan_part<CPLX, OPA_C, false>(m, pc.n, k, pc.bn_cols, num_cu, min_rounds).ws_bytes;
             // + the operand-sum plane of a 3M launch (whether a product runs on three multiplications depends on the phase
             // tag, which the sizing does not know: counted for every complex product while 3M is enabled)
-            if (CHASE_M3_SPLANE && gemm3m_enabled() != 0) b = ((b + 255) & ~(size_t)255) + splane_bytes(pc.n, k, pc.bn_cols);
+            if (gemm3m_enabled() != 0) b = ((b + 255) & ~(size_t)255) + splane_bytes(pc.n, k, pc.bn_cols);
         }
         need = std::max(need, b);
     }

@@ -1,5 +1,7 @@
-"""The plane-fed 3M kernel (round 6) against round 2-5's loop (-DCHASE_M3_SPLANE=0 variant library): the same products must come out
-BIT FOR BIT (the plane holds the same IEEE sums, accumulators are independent).  Run once per library, compare the printed hashes.
+"""Content hashes of 26 three-multiplication products (13 shapes in phases 1 and 2): the generator of tests/golden/gemm3m_hashes.json.
+Round 6 ran it on the plane-fed 3M loop and on the loop it replaced (in git at commit 258a299 and earlier) and got the same hashes
+BIT FOR BIT (the plane holds the same IEEE sums, accumulators are independent).  To compare another build of the library, run once
+per library and compare the printed hashes.
 usage: [CHASE_HIP_LIB=...] python scripts/r06_gemm_bitwise.py"""
 import os
 import sys

@@ -1,9 +1,9 @@
 """The MFMA GEMM kernels must fit their registers: no instantiation of gemm_f64_kernel may touch scratch inside a loop.
-Round 3's verdict found one spilled VGPR in the two ragged three-multiplication op = C instantiations; round 4 looked at where it
-sits: one store before the K loops and one load after them (a value parked across the loop), nothing in any loop - and the form
-without it is 3 % slower on all-ragged launches (profiles/r04_ragged_c_compare.txt), so it stays, and this test pins the
-placement: every other instantiation has no scratch at all, and no scratch instruction of any instantiation sits in a basic block
-that the compiler marks as part of a loop.  Cross-compiles the file to gfx950 assembly - no GPU needed."""
+The ragged three-multiplication instantiations keep a few VGPRs in scratch, but only parked across the K loops: stored before
+them, loaded after them, nothing in any loop (an earlier 3M loop did the same with one register, and the form without it was 3 %
+slower on all-ragged launches: profiles/r04_ragged_c_compare.txt).  This test pins the placement: every other instantiation has no
+scratch at all, and no scratch instruction of any instantiation sits in a basic block that the compiler marks as part of a loop.
+Cross-compiles the file to gfx950 assembly - no GPU needed."""
 import os
 import re
 import subprocess
@@ -12,9 +12,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-# Round 6 (plane-fed 3M loop, 80 KB of LDS, sum fragments next to 192 accumulators): the four RAGGED 3M instantiations park up to
-# five registers the same way (stores before the K loops, loads after them); the whole-tile ones - 99 % of the filter's time - have
-# no scratch at all.
+# The plane-fed 3M loop (80 KB of LDS, sum fragments next to 192 accumulators): the four RAGGED 3M instantiations park up to five
+# registers (stores before the K loops, loads after them); the whole-tile ones - 99 % of the filter's time - have no scratch at all.
 PARKED = ("ILb1ELb1ELi0ELb1ELb1ELb0E", "ILb1ELb1ELi1ELb1ELb1ELb0E",     # <cplx, op=C, tag 0 / 1, ragged, 3M, not narrow>
           "ILb1ELb0ELi0ELb1ELb1ELb0E", "ILb1ELb0ELi1ELb1ELb1ELb0E")     # <cplx, op=N, tag 0 / 1, ragged, 3M, not narrow>
 
