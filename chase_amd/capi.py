@@ -328,6 +328,11 @@ _sig("chase_hip_col_nrm2", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_lon
 _sig("chase_hip_col_axpy", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_double, c_void_p, c_long,
      c_void_p, c_long)
 _sig("chase_hip_col_scal", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_long)
+_sig("chase_hip_col_sumsq", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p)
+_sig("chase_hip_sqrt_inplace", c_int, c_void_p, c_void_p, c_int)
+_sig("chase_hip_fill_normal_bc", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_long, c_int, c_int, c_int,
+     C.c_ulonglong)
+_sig("chase_hip_rows_indexed", c_int, c_void_p, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_int)
 _sig("chase_hip_pack_upper", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p)
 _sig("chase_hip_unpack_upper", c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_long, c_int)
 

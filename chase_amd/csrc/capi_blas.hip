@@ -131,6 +131,9 @@ int chase_hip_rows_indexed(chase_hip_ctx* c, int cplx, const void* in, long ld_i
     if (!c) return set_error(CHASE_HIP_EINVAL, "rows_indexed: NULL ctx");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("rows_indexed", np, ncols, scatter, 0);
+    if (np < 0 || ncols < 0 || ld_in < 0 || ld_out < 0) return set_error(CHASE_HIP_EINVAL, "rows_indexed: bad shape");
+    if (np == 0 || ncols == 0) return 0;
+    if (!in || !out || !idx_dev) return set_error(CHASE_HIP_EINVAL, "rows_indexed: NULL argument");
     KCHK(rows_indexed(c->stream, cplx != 0, (const double*)in, ld_in, (double*)out, ld_out, idx_dev, np, ncols, scatter),
          "rows_indexed");
     return 0;
@@ -269,7 +272,9 @@ int chase_hip_shift_list(chase_hip_ctx* c, int cplx, void* H, long ldh, const in
     if (!c) return set_error(CHASE_HIP_EINVAL, "shift_list: NULL ctx");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("shift_list", cnt, 0, 0, 0);
-    if (cnt < 0) return set_error(CHASE_HIP_EINVAL, "shift_list: negative count");
+    if (cnt < 0 || ldh < 0) return set_error(CHASE_HIP_EINVAL, "shift_list: negative count or leading dimension");
+    if (cnt == 0) return 0;
+    if (!H || !rows_dev || !cols_dev) return set_error(CHASE_HIP_EINVAL, "shift_list: NULL argument");
     KCHK(shift_list(c->stream, (double*)H, ldh, rows_dev, cols_dev, cnt, ept_of(cplx), shift), "shift_list");
     return 0;
 }
@@ -389,6 +394,10 @@ int chase_hip_scale_rows(chase_hip_ctx* c, int cplx, int m, int n, void* X, long
     if (!c) return set_error(CHASE_HIP_EINVAL, "scale_rows: NULL ctx");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("scale_rows", m, n, row0, 0);
+    if (m < 0 || n < 0 || row0 < 0) return set_error(CHASE_HIP_EINVAL, "scale_rows: negative extent");
+    if (m == 0 || n == 0) return 0;
+    if (ldx < m) return set_error(CHASE_HIP_EINVAL, "scale_rows: bad shape");
+    if (!X) return set_error(CHASE_HIP_EINVAL, "scale_rows: NULL matrix");
     const int e = ept_of(cplx);
     KCHK(scale_rows(c->stream, (double*)X, ldx * e, (long)row0 * e, (long)m * e, n, s), "scale_rows");
     return 0;
@@ -400,7 +409,10 @@ int chase_hip_scale_rows_bc(chase_hip_ctx* c, int cplx, int m, int n, void* X, l
     if (!c) return set_error(CHASE_HIP_EINVAL, "scale_rows_bc: NULL ctx");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("scale_rows_bc", m, n, 0, 0);
+    if (m < 0 || n < 0) return set_error(CHASE_HIP_EINVAL, "scale_rows_bc: negative extent");
     if (nb <= 0 || p <= 0 || q < 0 || q >= p || (n > 0 && ldx < m)) return set_error(CHASE_HIP_EINVAL, "scale_rows_bc: bad layout");
+    if (m == 0 || n == 0) return 0;
+    if (!X) return set_error(CHASE_HIP_EINVAL, "scale_rows_bc: NULL matrix");
     const int e = ept_of(cplx);
     KCHK(scale_rows_bc(c->stream, (double*)X, ldx * e, (long)m, n, e, g0, nb, p, q, s), "scale_rows_bc");
     return 0;
@@ -457,6 +469,8 @@ int chase_hip_abs_trace(chase_hip_ctx* c, int cplx, int n, const void* A, long l
     if (!c || !out_host) return set_error(CHASE_HIP_EINVAL, "abs_trace: NULL argument");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("abs_trace", n, 0, 0, 0);
+    if (n < 0 || lda < n) return set_error(CHASE_HIP_EINVAL, "abs_trace: bad shape");
+    if (n > 0 && !A) return set_error(CHASE_HIP_EINVAL, "abs_trace: NULL matrix");
     RCCHK(c->ensure_buf(chase_hip_ctx::BUF_SCAL, 4096));
     double* d = (double*)c->bufs[chase_hip_ctx::BUF_SCAL];
     KCHK(abs_trace(c->stream, (const double*)A, lda, n, ept_of(cplx), d), "abs_trace");
@@ -593,7 +607,10 @@ int chase_hip_resid_norms(chase_hip_ctx* c, int cplx, int m, int n, const void* 
     if (!c || !resid_host || (V && !lambda_host)) return set_error(CHASE_HIP_EINVAL, "resid_norms: NULL argument");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("resid_norms", m, n, squared, 0);
-    if (n <= 0) return 0;
+    if (m < 0 || n < 0) return set_error(CHASE_HIP_EINVAL, "resid_norms: negative extent");
+    if (n == 0) return 0;
+    if (ldw < m || (V && ldv < m)) return set_error(CHASE_HIP_EINVAL, "resid_norms: leading dimension smaller than m");
+    if (m > 0 && !W) return set_error(CHASE_HIP_EINVAL, "resid_norms: NULL matrix");
     const int e = ept_of(cplx);
     RCCHK(c->ensure_buf(chase_hip_ctx::BUF_LAMBDA, (size_t)2 * n * sizeof(double)));
     double* dl = (double*)c->bufs[chase_hip_ctx::BUF_LAMBDA];
@@ -614,7 +631,10 @@ int chase_hip_resid_norms_dev(chase_hip_ctx* c, int cplx, int m, int n, const vo
     if (!c || !out_dev || (V && !lambda_host)) return set_error(CHASE_HIP_EINVAL, "resid_norms_dev: NULL argument");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("resid_norms_dev", m, n, squared, 0);
-    if (n <= 0) return 0;
+    if (m < 0 || n < 0) return set_error(CHASE_HIP_EINVAL, "resid_norms_dev: negative extent");
+    if (n == 0) return 0;
+    if (ldw < m || (V && ldv < m)) return set_error(CHASE_HIP_EINVAL, "resid_norms_dev: leading dimension smaller than m");
+    if (m > 0 && !W) return set_error(CHASE_HIP_EINVAL, "resid_norms_dev: NULL matrix");
     const int e = ept_of(cplx);
     RCCHK(c->ensure_buf(chase_hip_ctx::BUF_LAMBDA, (size_t)2 * n * sizeof(double)));
     double* dl = (double*)c->bufs[chase_hip_ctx::BUF_LAMBDA];
@@ -738,9 +758,12 @@ int chase_hip_pseudo_rr_small(chase_hip_ctx* c, int cplx, int n, void* A_dev, vo
 /* A (n x n device, ld lda) <- identity */
 int chase_hip_set_identity(chase_hip_ctx* c, int cplx, int n, void* A, long lda)
 {
-    if (!c || !A) return set_error(CHASE_HIP_EINVAL, "set_identity: NULL argument");
+    if (!c) return set_error(CHASE_HIP_EINVAL, "set_identity: NULL ctx");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("set_identity", n, 0, 0, 0);
+    if (n < 0 || lda < n) return set_error(CHASE_HIP_EINVAL, "set_identity: bad shape");
+    if (n == 0) return 0;
+    if (!A) return set_error(CHASE_HIP_EINVAL, "set_identity: NULL matrix");
     HIPCHK(hipMemset2DAsync(A, (size_t)lda * sizeof(double) * ept_of(cplx), 0, (size_t)n * sizeof(double) * ept_of(cplx), n, c->stream));
     KCHK(shift_diag(c->stream, (double*)A, lda, n, ept_of(cplx), 1.0), "set_identity");
     return 0;
@@ -777,6 +800,10 @@ int chase_hip_col_dot(chase_hip_ctx* c, int cplx, int m, int n, const void* X, l
     if (!c) return set_error(CHASE_HIP_EINVAL, "col_dot: NULL ctx");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("col_dot", m, n, 0, 0);
+    if (m < 0 || n < 0) return set_error(CHASE_HIP_EINVAL, "col_dot: negative extent");
+    if (n == 0) return 0;
+    if (ldx < m || ldy < m) return set_error(CHASE_HIP_EINVAL, "col_dot: leading dimension smaller than m");
+    if (!out_dev || (m > 0 && (!X || !Y))) return set_error(CHASE_HIP_EINVAL, "col_dot: NULL argument");   // m == 0: zeros
     const int e = ept_of(cplx);
     KCHK(col_dot(c->stream, cplx != 0, (const double*)X, ldx * e, (const double*)Y, ldy * e, m, n, out_dev), "col_dot");
     return 0;
@@ -786,6 +813,10 @@ int chase_hip_col_nrm2(chase_hip_ctx* c, int cplx, int m, int n, const void* X, 
     if (!c) return set_error(CHASE_HIP_EINVAL, "col_nrm2: NULL ctx");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("col_nrm2", m, n, 0, 0);
+    if (m < 0 || n < 0) return set_error(CHASE_HIP_EINVAL, "col_nrm2: negative extent");
+    if (n == 0) return 0;
+    if (ldx < m) return set_error(CHASE_HIP_EINVAL, "col_nrm2: leading dimension smaller than m");
+    if (!out_dev || (m > 0 && !X)) return set_error(CHASE_HIP_EINVAL, "col_nrm2: NULL argument");                 // m == 0: zeros
     const int e = ept_of(cplx);
     KCHK(resid_norms(c->stream, (const double*)X, ldx * e, nullptr, 0, nullptr, (long)m * e, n, out_dev, 1), "col_nrm2");
     return 0;
@@ -796,6 +827,10 @@ int chase_hip_col_sumsq(chase_hip_ctx* c, int cplx, int m, int n, const void* X,
     if (!c) return set_error(CHASE_HIP_EINVAL, "col_sumsq: NULL ctx");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("col_sumsq", m, n, 0, 0);
+    if (m < 0 || n < 0) return set_error(CHASE_HIP_EINVAL, "col_sumsq: negative extent");
+    if (n == 0) return 0;
+    if (ldx < m) return set_error(CHASE_HIP_EINVAL, "col_sumsq: leading dimension smaller than m");
+    if (!out_dev || (m > 0 && !X)) return set_error(CHASE_HIP_EINVAL, "col_sumsq: NULL argument");                 // m == 0: zeros
     const int e = ept_of(cplx);
     KCHK(resid_norms(c->stream, (const double*)X, ldx * e, nullptr, 0, nullptr, (long)m * e, n, out_dev, 0), "col_sumsq");
     return 0;
@@ -805,6 +840,9 @@ int chase_hip_sqrt_inplace(chase_hip_ctx* c, double* x_dev, int n)
     if (!c) return set_error(CHASE_HIP_EINVAL, "sqrt_inplace: NULL ctx");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("sqrt_inplace", n, 0, 0, 0);
+    if (n < 0) return set_error(CHASE_HIP_EINVAL, "sqrt_inplace: negative extent");
+    if (n == 0) return 0;
+    if (!x_dev) return set_error(CHASE_HIP_EINVAL, "sqrt_inplace: NULL argument");
     KCHK(sqrt_inplace(c->stream, x_dev, n), "sqrt_inplace");
     return 0;
 }
@@ -814,6 +852,11 @@ int chase_hip_col_axpy(chase_hip_ctx* c, int cplx, int m, int n, const double* a
     if (!c) return set_error(CHASE_HIP_EINVAL, "col_axpy: NULL ctx");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("col_axpy", m, n, a_is_real, 0);
+    if (m < 0 || n < 0) return set_error(CHASE_HIP_EINVAL, "col_axpy: negative extent");
+    if (a_stride < 0) return set_error(CHASE_HIP_EINVAL, "col_axpy: negative a_stride");
+    if (n == 0) return 0;
+    if (ldx < m || ldy < m) return set_error(CHASE_HIP_EINVAL, "col_axpy: leading dimension smaller than m");
+    if (m > 0 && (!a_dev || !X || !Y)) return set_error(CHASE_HIP_EINVAL, "col_axpy: NULL argument");
     const int e = ept_of(cplx);
     KCHK(col_axpy(c->stream, cplx != 0, a_dev, a_is_real, a_stride, sgn, (const double*)X, ldx * e, (double*)Y, ldy * e,
                   m, n), "col_axpy");
@@ -824,6 +867,10 @@ int chase_hip_col_scal(chase_hip_ctx* c, int cplx, int m, int n, const double* a
     if (!c) return set_error(CHASE_HIP_EINVAL, "col_scal: NULL ctx");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("col_scal", m, n, inverse, 0);
+    if (m < 0 || n < 0) return set_error(CHASE_HIP_EINVAL, "col_scal: negative extent");
+    if (n == 0) return 0;
+    if (ldx < m) return set_error(CHASE_HIP_EINVAL, "col_scal: leading dimension smaller than m");
+    if (m > 0 && (!a_dev || !X)) return set_error(CHASE_HIP_EINVAL, "col_scal: NULL argument");
     const int e = ept_of(cplx);
     KCHK(col_scal(c->stream, a_dev, inverse, (double*)X, ldx * e, (long)m * e, n), "col_scal");
     return 0;
@@ -835,6 +882,9 @@ int chase_hip_pack_upper(chase_hip_ctx* c, int cplx, int n, const void* A, long 
     if (!c) return set_error(CHASE_HIP_EINVAL, "pack_upper: NULL ctx");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("pack_upper", n, 0, 0, 0);
+    if (n < 0 || lda < n) return set_error(CHASE_HIP_EINVAL, "pack_upper: bad shape");
+    if (n == 0) return 0;
+    if (!A || !P) return set_error(CHASE_HIP_EINVAL, "pack_upper: NULL argument");
     KCHK(pack_upper(c->stream, (const double*)A, lda, n, ept_of(cplx), (double*)P), "pack_upper");
     return 0;
 }
@@ -843,6 +893,9 @@ int chase_hip_unpack_upper(chase_hip_ctx* c, int cplx, int n, const void* P, voi
     if (!c) return set_error(CHASE_HIP_EINVAL, "unpack_upper: NULL ctx");
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (c->oplog_on) c->oplog_add("unpack_upper", n, mirror, 0, 0);
+    if (n < 0 || lda < n) return set_error(CHASE_HIP_EINVAL, "unpack_upper: bad shape");
+    if (n == 0) return 0;
+    if (!P || !A) return set_error(CHASE_HIP_EINVAL, "unpack_upper: NULL argument");
     KCHK(unpack_upper(c->stream, (double*)P, n, ept_of(cplx), (double*)A, lda), "unpack_upper");
     if (mirror) KCHK(mirror_upper(c->stream, (double*)A, lda, n, ept_of(cplx)), "mirror_upper");
     return 0;

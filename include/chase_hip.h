@@ -12,6 +12,9 @@
  *   - "dev" pointers are HIP device pointers; "host" pointers are ordinary host memory.
  *   - all device work is enqueued on the context's HIP stream; entry points that return scalars to the host
  *     synchronise that stream themselves, the others are asynchronous.
+ *   - arguments are checked on the host before anything is enqueued: a negative extent, a leading dimension smaller than the
+ *     row count or a NULL matrix / index list of a non-empty operand is CHASE_HIP_EINVAL.  An empty operand (n == 0) returns 0
+ *     whatever its pointers; the column kernels accept m == 0 with n > 0 (a rank without local rows: dots and norms are 0).
  */
 #ifndef CHASE_HIP_H
 #define CHASE_HIP_H
