@@ -71,6 +71,11 @@ _sig("chase_hip_gemm_s", c_int, c_void_p, c_char, c_int, c_int, c_int, C.c_float
      C.c_float, c_void_p, c_long)
 _sig("chase_hip_gemm_c", c_int, c_void_p, c_char, c_int, c_int, c_int, P(C.c_float), c_void_p, c_long, c_void_p,
      c_long, P(C.c_float), c_void_p, c_long)
+_sig("chase_hip_gemm_sd", c_int, c_void_p, c_char, c_int, c_int, c_int, c_double, c_void_p, c_long, c_void_p, c_long,
+     c_double, c_void_p, c_long)
+_sig("chase_hip_gemm_cz", c_int, c_void_p, c_char, c_int, c_int, c_int, P(c_double), c_void_p, c_long, c_void_p,
+     c_long, P(c_double), c_void_p, c_long)
+_sig("chase_hip_diag_list_d2s", c_int, c_void_p, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_int)
 _sig("chase_hip_convert_d2s", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
 _sig("chase_hip_convert_s2d", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
 _sig("chase_hip_diag_d2s", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
@@ -211,6 +216,18 @@ class Context:
             check(lib.chase_hip_gemm_c(self.h, op, m, n, k, _c2(alpha), A, lda, B, ldb, _c2(beta), Cm, ldc), "gemm_c")
         else:
             check(lib.chase_hip_gemm_s(self.h, op, m, n, k, float(alpha), A, lda, B, ldb, float(beta), Cm, ldc), "gemm_s")
+
+    def gemm32w(self, opA, m, n, k, alpha, A, lda, B, ldb, beta, Cm, ldc, cplx):
+        """fp32 operands, fp64 result and scalars, op(A) = N or C (the grid filter's product): device addresses (ints)."""
+        op = opA.encode()[0:1]
+        if cplx:
+            check(lib.chase_hip_gemm_cz(self.h, op, m, n, k, _z2(alpha), A, lda, B, ldb, _z2(beta), Cm, ldc), "gemm_cz")
+        else:
+            check(lib.chase_hip_gemm_sd(self.h, op, m, n, k, float(alpha), A, lda, B, ldb, float(beta), Cm, ldc), "gemm_sd")
+
+    def diag_list_d2s(self, H, ldh, Hs, ldhs, rows, cols, cnt, cplx):
+        """Hs[rows[i], cols[i]] (fp32) = H[rows[i], cols[i]] (fp64), i < cnt; rows, cols: device addresses of int32 lists."""
+        check(lib.chase_hip_diag_list_d2s(self.h, int(cplx), H, ldh, Hs, ldhs, rows, cols, cnt), "diag_list_d2s")
 
     def convert_d2s(self, m, n, src, ld_src, dst, ld_dst, cplx):
         """dst (fp32) = src (fp64), round to nearest; device addresses, leading dimensions in elements."""

@@ -327,6 +327,19 @@ int chase_hip_diag_d2s(chase_hip_ctx* c, int cplx, int n, const void* H, long ld
     return 0;
 }
 
+int chase_hip_diag_list_d2s(chase_hip_ctx* c, int cplx, const void* H, long ldh, void* Hs, long ldhs, const int* rows_dev,
+                            const int* cols_dev, int cnt)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "diag_list_d2s: NULL ctx");
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    if (c->oplog_on) c->oplog_add("diag_list_d2s", cnt, 0, 0, 0);
+    if (cnt < 0 || ldh < 0 || ldhs < 0) return set_error(CHASE_HIP_EINVAL, "diag_list_d2s: negative count or leading dimension");
+    if (cnt == 0) return 0;
+    if (!H || !Hs || !rows_dev || !cols_dev) return set_error(CHASE_HIP_EINVAL, "diag_list_d2s: NULL argument");
+    KCHK(diag_list_d2s(c->stream, (const double*)H, ldh, (float*)Hs, ldhs, rows_dev, cols_dev, cnt, ept_of(cplx)), "diag_list_d2s");
+    return 0;
+}
+
 int chase_hip_swap_cols(chase_hip_ctx* c, int cplx, int m, void* V, long ldv, long i, long j)
 {
     if (!c || !V) return set_error(CHASE_HIP_EINVAL, "swap_cols: NULL argument");

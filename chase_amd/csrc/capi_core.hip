@@ -284,6 +284,39 @@ int chase_hip_gemm_c(chase_hip_ctx* c, char opA, int m, int n, int k, const floa
     return gemm32(c, true, opA, m, n, k, alpha, (const float*)A, lda, (const float*)B, ldb, beta, (float*)C, ldc);
 }
 
+// fp32 operands, fp64 result and scalars, op(A) = N or C: the filter product of the grid solver
+static int gemm32w(chase_hip_ctx* c, bool cplx, char opA, int m, int n, int k, const double* alpha, const float* A, long lda,
+                   const float* B, long ldb, const double* beta, double* C, long ldc)
+{
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    const bool opn = opA == 'N' || opA == 'n';
+    const bool opc = opA == 'C' || opA == 'c' || (!cplx && (opA == 'T' || opA == 't'));
+    if (!opn && !opc)
+        return set_error(CHASE_HIP_EINVAL, cplx ? "gemm_cz: opA must be 'N' or 'C'" : "gemm_sd: opA must be 'N', 'C' or 'T'");
+    int rc = check_gemm(opA, m, n, k, A, lda, B, ldb, C, ldc);
+    if (rc || m == 0 || n == 0) return rc;
+    if (c->oplog_on) c->oplog_add(cplx ? (opn ? "gemm_czN" : "gemm_czC") : (opn ? "gemm_sdN" : "gemm_sdC"), m, n, k, c->phase * 100);
+    int e = gemm_f32w(c->stream, cplx, opA, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, c->num_cu, c->phase == 1 ? 1 : 0);
+    if (e == GEMM_F32_EOP) return set_error(CHASE_HIP_EINVAL, "gemm_sd / gemm_cz: bad opA");
+    if (e) return hip_fail((hipError_t)e, "gemm_f32w launch");
+    return 0;
+}
+
+int chase_hip_gemm_sd(chase_hip_ctx* c, char opA, int m, int n, int k, double alpha, const float* A, long lda, const float* B,
+                      long ldb, double beta, double* C, long ldc)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "ctx == NULL");
+    return gemm32w(c, false, opA, m, n, k, &alpha, A, lda, B, ldb, &beta, C, ldc);
+}
+
+int chase_hip_gemm_cz(chase_hip_ctx* c, char opA, int m, int n, int k, const double alpha[2], const void* A, long lda,
+                      const void* B, long ldb, const double beta[2], void* C, long ldc)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "ctx == NULL");
+    if (!alpha || !beta) return set_error(CHASE_HIP_EINVAL, "gemm_cz: NULL alpha/beta");
+    return gemm32w(c, true, opA, m, n, k, alpha, (const float*)A, lda, (const float*)B, ldb, beta, (double*)C, ldc);
+}
+
 /* bytes of split-K workspace chase_hip_gemm_{d,z} uses for this shape on a device with num_cu compute units (a pure function
  * of the shape: the launcher never picks another split to fit what happens to be allocated) */
 size_t chase_hip_gemm_workspace_bytes(int cplx, char opA, int m, int n, int k, int num_cu, int min_rounds)

@@ -2,7 +2,15 @@
 // mixed-precision Chebyshev filter (ChaseHip::HEMM while the filter call runs in fp32).  Reference: the cublasSgemm / cublasCgemm
 // the reference's mixed-precision HEMM issues on its shadow copies (Impl/pchase_gpu/pchase_gpu.hpp:785-901).
 //
-//   C = alpha * A * B + beta * C      column-major, op(A) = N only, real fp32 or interleaved (re, im) complex fp32
+//   C = alpha * A * B + beta * C           column-major, op(A) = N, real fp32 or interleaved (re, im) complex fp32     (gemm_f32)
+//   C64 = alpha * op(A) * B + beta * C64   op(A) = N or C, A and B fp32, C / alpha / beta fp64                        (gemm_f32w)
+//
+// The second form is the product of the filter on a process grid (pChaseHip): every rank's partial product leaves the kernel in
+// fp64 and is summed over the ranks in fp64 by the collectives the fp64 path already has.  OPC reads A as a k x m array
+// (contiguous in k: the access pattern of the B tile) and transposes it into the same m-contiguous LDS image the op = N path
+// builds: lane l of a 32-lane half stores dword l of an LDS row, one conflict-free ds_write_b32 group, exactly the stores of the
+// B tile - the transposition costs no bank conflict that op = N does not have, and the fragment reads are unchanged.  The
+// conjugation is the sign of the imaginary plane, applied once at that store, not per MFMA.  WIDE only changes the epilogue.
 //
 // One 256-thread workgroup owns a 128 x BN output tile (BN = 128 or 64) over the WHOLE K: no split-K, no atomics, one fixed
 // summation order per element - results are bitwise reproducible run to run.  Each of the four waves owns 64 x BN/2 of the tile
@@ -31,13 +39,16 @@ struct Args {
     const float* A; long lda;
     const float* B; long ldb;
     float* C; long ldc;
+    double war, wai, wbr, wbi;     // WIDE: fp64 scalars and an fp64 C (ldc in its elements)
+    double* Cw;
     int gn;                        // tiles along n
     unsigned total;                // tiles
     int vecA, vecB, vecC;          // 16-byte accesses allowed (base pointer and leading dimension)
 };
 
 // TAG only gives the launches of the Chebyshev filter (context phase 1) a kernel symbol of their own (profiles list them apart)
-template <bool CPLX, int WN, int TAG>
+// OPC: op(A) = A^H from a k x m array.  WIDE: epilogue in fp64 on an fp64 C.
+template <bool CPLX, int WN, int TAG, bool OPC = false, bool WIDE = false>
 __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const Args a)
 {
     constexpr int BN = 64 * WN;
@@ -77,8 +88,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const Args a)
     auto load_fast = [&](long k0) {
         #pragma unroll
         for (int r = 0; r < 2; ++r) {
-            const int f = tid + 256 * r, rg = f % RG, kk = f / RG;
-            ga[r] = *(const float4*)(a.A + E * (m0 + (long)EPV * rg + (k0 + kk) * a.lda));
+            if constexpr (OPC) {
+                const int f = tid + 256 * r, j = f % BM, kq = f / BM;
+                ga[r] = *(const float4*)(a.A + E * (k0 + (long)EPV * kq + (m0 + j) * a.lda));
+            } else {
+                const int f = tid + 256 * r, rg = f % RG, kk = f / RG;
+                ga[r] = *(const float4*)(a.A + E * (m0 + (long)EPV * rg + (k0 + kk) * a.lda));
+            }
         }
         #pragma unroll
         for (int r = 0; r < WN; ++r) {
@@ -89,10 +105,30 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const Args a)
     auto load_slow = [&](long k0) {
         #pragma unroll
         for (int r = 0; r < 2; ++r) {
+            float v[4] = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (OPC) {
+                const int f = tid + 256 * r, j = f % BM, kq = f / BM;
+                const long col = m0 + j, kg = k0 + (long)EPV * kq;
+                const float* p = a.A + E * (kg + col * a.lda);
+                if (col < a.m) {
+                    if (a.vecA && kg + EPV <= a.k) {
+                        const float4 t = *(const float4*)p;
+                        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+                    } else {
+                        #pragma unroll
+                        for (int e = 0; e < EPV; ++e)
+                            if (kg + e < a.k) {
+                                #pragma unroll
+                                for (int c = 0; c < E; ++c) v[E * e + c] = p[E * e + c];
+                            }
+                    }
+                }
+                ga[r] = make_float4(v[0], v[1], v[2], v[3]);
+                continue;
+            }
             const int f = tid + 256 * r, rg = f % RG, kk = f / RG;
             const long row = m0 + (long)EPV * rg, kg = k0 + kk;
             const float* p = a.A + E * (row + kg * a.lda);
-            float v[4] = {0.f, 0.f, 0.f, 0.f};
             if (kg < a.k) {
                 if (a.vecA && row + EPV <= a.m) {
                     const float4 t = *(const float4*)p;
@@ -133,6 +169,22 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const Args a)
     auto store_tiles = [&](int buf) {
         #pragma unroll
         for (int r = 0; r < 2; ++r) {
+            if constexpr (OPC) {
+                // the k-contiguous vector of column j goes to rows of the image at dword j: 32 consecutive dwords per lane half
+                const int f = tid + 256 * r, j = f % BM, kq = f / BM;
+                if constexpr (CPLX) {
+                    sA[buf][(2 * kq) * LDA_T + j] = ga[r].x;
+                    sA[buf][(BK + 2 * kq) * LDA_T + j] = -ga[r].y;           // conj
+                    sA[buf][(2 * kq + 1) * LDA_T + j] = ga[r].z;
+                    sA[buf][(BK + 2 * kq + 1) * LDA_T + j] = -ga[r].w;
+                } else {
+                    sA[buf][(4 * kq) * LDA_T + j] = ga[r].x;
+                    sA[buf][(4 * kq + 1) * LDA_T + j] = ga[r].y;
+                    sA[buf][(4 * kq + 2) * LDA_T + j] = ga[r].z;
+                    sA[buf][(4 * kq + 3) * LDA_T + j] = ga[r].w;
+                }
+                continue;
+            }
             const int f = tid + 256 * r, rg = f % RG, kk = f / RG;
             if constexpr (CPLX) {
                 *(float2*)&sA[buf][kk * LDA_T + 2 * rg] = make_float2(ga[r].x, ga[r].z);
@@ -226,6 +278,70 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const Args a)
     }
 
     // epilogue.  C/D map of the 32 x 32 tile: column = lane & 31, rows 8 g + 4 (lane >> 5) + (0..3) in registers 4 g .. 4 g + 3
+    if constexpr (WIDE) {
+        const bool useC = (a.wbr != 0.0) || (a.wbi != 0.0);
+        #pragma unroll
+        for (int i = 0; i < 2; ++i)
+            #pragma unroll
+            for (int j = 0; j < WN; ++j) {
+                const long col = n0 + wn * (32 * WN) + 32 * j + lr;
+                if (col >= a.n) continue;
+                #pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const long row = m0 + wm * 64 + 32 * i + 8 * g + 4 * lh;
+                    if (row >= a.m) continue;
+                    double* c = a.Cw + E * (row + col * a.ldc);
+                    const bool vec = a.vecC && row + 4 <= a.m;
+                    double o[4 * E], c0[4 * E];
+                    #pragma unroll
+                    for (int q = 0; q < 4 * E; ++q) c0[q] = 0.0;
+                    if (useC) {
+                        if (vec) {
+                            #pragma unroll
+                            for (int q = 0; q < 2 * E; ++q) {
+                                const double2 t = ((const double2*)c)[q];
+                                c0[2 * q] = t.x; c0[2 * q + 1] = t.y;
+                            }
+                        } else {
+                            #pragma unroll
+                            for (int e = 0; e < 4; ++e)
+                                if (row + e < a.m) {
+                                    #pragma unroll
+                                    for (int p = 0; p < E; ++p) c0[E * e + p] = c[E * e + p];
+                                }
+                        }
+                    }
+                    #pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if constexpr (CPLX) {
+                            const double xr = (double)acc[i][j][0][4 * g + e], xi = (double)acc[i][j][1][4 * g + e];
+                            double yr = a.war * xr - a.wai * xi, yi = a.war * xi + a.wai * xr;
+                            if (useC) {
+                                yr += a.wbr * c0[2 * e] - a.wbi * c0[2 * e + 1];
+                                yi += a.wbr * c0[2 * e + 1] + a.wbi * c0[2 * e];
+                            }
+                            o[2 * e] = yr; o[2 * e + 1] = yi;
+                        } else {
+                            double y = a.war * (double)acc[i][j][0][4 * g + e];
+                            if (useC) y += a.wbr * c0[e];
+                            o[e] = y;
+                        }
+                    }
+                    if (vec) {
+                        #pragma unroll
+                        for (int q = 0; q < 2 * E; ++q) ((double2*)c)[q] = make_double2(o[2 * q], o[2 * q + 1]);
+                    } else {
+                        #pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (row + e < a.m) {
+                                #pragma unroll
+                                for (int p = 0; p < E; ++p) c[E * e + p] = o[E * e + p];
+                            }
+                    }
+                }
+            }
+        return;
+    }
     const bool useC = (a.br != 0.f) || (a.bi != 0.f);
     #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -289,11 +405,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const Args a)
         }
 }
 
-template <bool CPLX, int WN>
+template <bool CPLX, int WN, bool OPC = false, bool WIDE = false>
 int launch(hipStream_t st, const Args& a, int tag)
 {
-    if (tag == 1) hipLaunchKernelGGL((gemm_f32_kernel<CPLX, WN, 1>), dim3(a.total), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gemm_f32_kernel<CPLX, WN, 0>), dim3(a.total), dim3(256), 0, st, a);
+    if (tag == 1) hipLaunchKernelGGL((gemm_f32_kernel<CPLX, WN, 1, OPC, WIDE>), dim3(a.total), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((gemm_f32_kernel<CPLX, WN, 0, OPC, WIDE>), dim3(a.total), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
 
@@ -312,7 +428,46 @@ int tile_cols(int m, int n, int num_cu)
     return r64 < r128 ? 64 : 128;
 }
 
+// the tile grid and the 16-byte flags of the fp32 operands (A: along m for op = N, along k for op = C - the same test on base
+// pointer and leading dimension); false: more tiles than a launch can hold
+bool plan(Args& a, bool cplx, int m, int n, int k, const float* A, long lda, const float* B, long ldb, int bn)
+{
+    a.m = m; a.n = n; a.k = k < 0 ? 0 : k;
+    a.A = A; a.lda = lda; a.B = B; a.ldb = ldb;
+    const long gm = ((long)m + BM - 1) / BM, gn = ((long)n + bn - 1) / bn;
+    if (gm * gn > 0x7fffffffL) return false;
+    a.gn = (int)gn;
+    a.total = (unsigned)(gm * gn);
+    const long ldmask = cplx ? 1 : 3;          // leading dimension in 16-byte units
+    a.vecA = (a.k > 0 && al16(A) && (lda & ldmask) == 0) ? 1 : 0;
+    a.vecB = (a.k > 0 && al16(B) && (ldb & ldmask) == 0) ? 1 : 0;
+    return true;
+}
+
 } // namespace
+
+int gemm_f32w(hipStream_t st, bool cplx, char opA, int m, int n, int k, const double* alpha, const float* A, long lda,
+              const float* B, long ldb, const double* beta, double* C, long ldc, int num_cu, int tag)
+{
+    const bool opn = opA == 'N' || opA == 'n';
+    const bool opc = opA == 'C' || opA == 'c' || (!cplx && (opA == 'T' || opA == 't'));
+    if (!opn && !opc) return GEMM_F32_EOP;
+    if (m <= 0 || n <= 0) return 0;
+    const int bn = tile_cols(m, n, num_cu);
+    Args a;
+    if (!plan(a, cplx, m, n, k, A, lda, B, ldb, bn)) return (int)hipErrorInvalidValue;
+    a.ar = a.ai = a.br = a.bi = 0.f; a.C = nullptr;
+    a.war = alpha[0]; a.wai = cplx ? alpha[1] : 0.0;
+    a.wbr = beta[0]; a.wbi = cplx ? beta[1] : 0.0;
+    a.Cw = C; a.ldc = ldc;
+    a.vecC = (al16(C) && (cplx || (ldc & 1) == 0)) ? 1 : 0;       // 16 bytes: two real / one complex fp64 element
+    if (cplx) {
+        if (opc) return bn == 64 ? launch<true, 1, true, true>(st, a, tag) : launch<true, 2, true, true>(st, a, tag);
+        return bn == 64 ? launch<true, 1, false, true>(st, a, tag) : launch<true, 2, false, true>(st, a, tag);
+    }
+    if (opc) return bn == 64 ? launch<false, 1, true, true>(st, a, tag) : launch<false, 2, true, true>(st, a, tag);
+    return bn == 64 ? launch<false, 1, false, true>(st, a, tag) : launch<false, 2, false, true>(st, a, tag);
+}
 
 int gemm_f32(hipStream_t st, bool cplx, char opA, int m, int n, int k, const float* alpha, const float* A, long lda, const float* B,
              long ldb, const float* beta, float* C, long ldc, int num_cu, int tag)
@@ -321,18 +476,12 @@ int gemm_f32(hipStream_t st, bool cplx, char opA, int m, int n, int k, const flo
     if (m <= 0 || n <= 0) return 0;
     const int bn = tile_cols(m, n, num_cu);
     Args a;
-    a.m = m; a.n = n; a.k = k < 0 ? 0 : k;
+    if (!plan(a, cplx, m, n, k, A, lda, B, ldb, bn)) return (int)hipErrorInvalidValue;
     a.ar = alpha[0]; a.ai = cplx ? alpha[1] : 0.f;
     a.br = beta[0]; a.bi = cplx ? beta[1] : 0.f;
-    a.A = A; a.lda = lda; a.B = B; a.ldb = ldb; a.C = C; a.ldc = ldc;
-    const long gm = ((long)m + BM - 1) / BM, gn = ((long)n + bn - 1) / bn;
-    if (gm * gn > 0x7fffffffL) return (int)hipErrorInvalidValue;
-    a.gn = (int)gn;
-    a.total = (unsigned)(gm * gn);
-    const long ldmask = cplx ? 1 : 3;          // leading dimension in 16-byte units
-    a.vecA = (a.k > 0 && al16(A) && (lda & ldmask) == 0) ? 1 : 0;
-    a.vecB = (a.k > 0 && al16(B) && (ldb & ldmask) == 0) ? 1 : 0;
-    a.vecC = (al16(C) && (ldc & ldmask) == 0) ? 1 : 0;
+    a.C = C; a.ldc = ldc;
+    a.war = a.wai = a.wbr = a.wbi = 0.0; a.Cw = nullptr;
+    a.vecC = (al16(C) && (ldc & (cplx ? 1 : 3)) == 0) ? 1 : 0;
     if (cplx) return bn == 64 ? launch<true, 1>(st, a, tag) : launch<true, 2>(st, a, tag);
     return bn == 64 ? launch<false, 1>(st, a, tag) : launch<false, 2>(st, a, tag);
 }

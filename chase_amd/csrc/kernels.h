@@ -35,6 +35,11 @@ int gemm_f64_plan(bool cplx, char opA, int m, int n, int k, long lda, long ldb, 
 constexpr int GEMM_F32_EOP = -77002;
 int gemm_f32(hipStream_t st, bool cplx, char opA, int m, int n, int k, const float* alpha, const float* A, long lda, const float* B,
              long ldb, const float* beta, float* C, long ldc, int num_cu, int tag = 0);
+// the same product written and scaled in fp64: C64 = alpha op(A32) B32 + beta C64, op(A) = N or C (real: T as well), A for
+// op = C a k x m array.  alpha / beta point to 1 or 2 host doubles.  The product of the filter on a grid: the partial products
+// of the ranks are summed in fp64.
+int gemm_f32w(hipStream_t st, bool cplx, char opA, int m, int n, int k, const double* alpha, const float* A, long lda,
+              const float* B, long ldb, const double* beta, double* C, long ldc, int num_cu, int tag = 0);
 
 int mfma_f64_peak(hipStream_t st, double* out, int blocks, int iters);
 int stream_copy(hipStream_t st, void* dst, const void* src, size_t bytes);
@@ -77,6 +82,8 @@ int mirror_lower(hipStream_t st, double* A, long lda, int n, int ept, int zero_d
 int convert_d2s(hipStream_t st, const double* src, long ld_src, float* dst, long ld_dst, long ms, int ncols);   // round to nearest
 int convert_s2d(hipStream_t st, const float* src, long ld_src, double* dst, long ld_dst, long ms, int ncols);   // exact
 int diag_d2s(hipStream_t st, const double* H, long ldh, float* Hs, long ldhs, int n, int ept);                  // Hs[i,i] = (float)H[i,i]
+// Hs[rows[i], cols[i]] = (float)H[rows[i], cols[i]], i < cnt (device lists: the diagonal inside a rank's block)
+int diag_list_d2s(hipStream_t st, const double* H, long ldh, float* Hs, long ldhs, const int* rows, const int* cols, int cnt, int ept);
 
 // ---- generators (gen_kernels.hip) ----
 int fill_normal(hipStream_t st, bool cplx, double* X, long ldx, int m, int n, long grow0, long gcol0, long gld,

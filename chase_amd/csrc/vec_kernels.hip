@@ -216,6 +216,17 @@ __global__ void diag_d2s_kernel(const double* __restrict__ H, long ldh, float* _
     d[0] = (float)s[0];
     if (ept == 2) d[1] = (float)s[1];
 }
+// the list form (the global diagonal inside a rank's block of a process grid): Hs[rows[i], cols[i]] = (float)H[rows[i], cols[i]]
+__global__ void diag_list_d2s_kernel(const double* __restrict__ H, long ldh, float* __restrict__ Hs, long ldhs,
+                                     const int* __restrict__ rows, const int* __restrict__ cols, int cnt, int ept)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cnt) return;
+    const double* s = H + ((long)cols[i] * ldh + rows[i]) * ept;
+    float* d = Hs + ((long)cols[i] * ldhs + rows[i]) * ept;
+    d[0] = (float)s[0];
+    if (ept == 2) d[1] = (float)s[1];
+}
 
 // swap two columns.  Reference: chase_gpu.hpp:1003-1005 (cublasTswap), chase_cpu.hpp:820-830
 __global__ __launch_bounds__(256) void swap_kernel(double* __restrict__ a, double* __restrict__ b, long md)
@@ -535,6 +546,12 @@ int convert_s2d(hipStream_t st, const float* src, long ld_src, double* dst, long
     if (ms <= 0 || ncols <= 0) return 0;
     const int vec = ((ld_src & 3) == 0) && ((ld_dst & 1) == 0) && (((uintptr_t)src & 15) == 0) && (((uintptr_t)dst & 15) == 0);
     hipLaunchKernelGGL(convert_s2d_kernel, grid2(ms, ncols), dim3(256), 0, st, src, ld_src, dst, ld_dst, ms, ncols, vec);
+    return (int)hipGetLastError();
+}
+int diag_list_d2s(hipStream_t st, const double* H, long ldh, float* Hs, long ldhs, const int* rows, const int* cols, int cnt, int ept)
+{
+    if (cnt <= 0) return 0;
+    hipLaunchKernelGGL(diag_list_d2s_kernel, dim3(cdiv(cnt, 256)), dim3(256), 0, st, H, ldh, Hs, ldhs, rows, cols, cnt, ept);
     return (int)hipGetLastError();
 }
 int diag_d2s(hipStream_t st, const double* H, long ldh, float* Hs, long ldhs, int n, int ept)

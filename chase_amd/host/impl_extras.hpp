@@ -17,7 +17,7 @@ struct HipImplExtras {
     virtual std::size_t hemm_calls() const = 0;
     virtual std::size_t hemm_reused_vecs() const { return 0; }   // filter columns served from RR's cached H V (no GEMM)
     virtual std::size_t resd_rechecked() const { return 0; }     // residuals re-taken from a fresh four-product H v (on the tolerance)
-    // mixed-precision filter (single-GPU Hermitian Impl only): false = this Impl has no fp32 path and `on` was not taken
+    // mixed-precision filter (the Hermitian Impls, single GPU and grid): false = this Impl has no fp32 path and `on` was not taken
     virtual bool set_mixed_precision(bool on) { return !on; }
     virtual bool mixed_precision() const { return false; }
     virtual std::size_t hemm_sp_calls() const { return 0; }      // fp32 filter products
@@ -53,7 +53,7 @@ inline void mixed_precision_env_ignored(const char* impl)
     static std::atomic<bool> said{false};          // (ranks of a grid may be threads of one process)
     const char* e = std::getenv("CHASE_HIP_MIXED_PRECISION");
     if (!e || std::atoi(e) == 0 || said.exchange(true)) return;
-    std::fprintf(stderr, "chase_hip: CHASE_HIP_MIXED_PRECISION is ignored by %s (single-GPU Hermitian solver only)\n", impl);
+    std::fprintf(stderr, "chase_hip: CHASE_HIP_MIXED_PRECISION is ignored by %s (Hermitian solvers only)\n", impl);
 }
 
 } // namespace chase_amd

@@ -22,6 +22,12 @@
 //   * host control flow (potrf info, Ritz values, residuals) is made identical on all ranks by tiny agreement
 //     collectives instead of relying on bitwise-identical replicas;
 //   * Swap() is deferred into one column permutation, Lanczos scalars stay on the device;
+//   * mixed-precision filter (reference: pchase_gpu.hpp:785-901, CHASE_ENABLE_MIXED_PRECISION at build time) behind the run-time
+//     switch of ChaseHip, default off: set_mixed_precision / CHASE_HIP_MIXED_PRECISION=1.  A filter call that starts while the
+//     smallest residual of the unlocked wanted pairs is above 1e-3 runs its local products on fp32 operands (a shadow of H_loc,
+//     the input panel converted on the way) on the f32-input matrix cores, but every rank's partial product is WRITTEN AND SUMMED
+//     IN FP64: the vector blocks, the all-reduces, the transports and the panel pipeline are those of the fp64 path, nothing is
+//     converted back, locked columns are never touched.  fp32 collectives (half the bytes) are a later step;
 //   * the Householder fallback pivots in the stacked row order and fuses each column's three scalar all-reduces into one.
 #pragma once
 #include <algorithm>
@@ -49,6 +55,7 @@ public:
     using R = Base<T>;
     static constexpr int CP = is_cplx<T>::value ? 1 : 0;
     static constexpr int E = CP ? 2 : 1;
+    using ST = std::conditional_t<is_cplx<T>::value, std::complex<float>, float>;      // element of the fp32 shadows
 
     struct Dim {                                      // 1D block-cyclic distribution of N indices over p ranks
         long N = 0, nb = 1; int p = 1, q = 0; long nloc = 0;
@@ -68,7 +75,7 @@ public:
     {
         if (!ctx || !grid || !H_loc || !ritzv) throw std::invalid_argument("pChaseHip: null argument");
         if (N == 0 || nevex_ == 0 || nc_ > N) throw std::invalid_argument("pChaseHip: need 0 < nev+nex <= N");
-        mixed_precision_env_ignored("the grid solvers");
+        if (const char* e = std::getenv("CHASE_HIP_MIXED_PRECISION")) mixed_ = std::atoi(e) != 0;   // (the pseudo Impl clears it)
         hip_ok(chase_hip_grid_info(grid, &nprow_, &npcol_, &myrow_, &mycol_), "grid_info");
         Rr_.N = Cc_.N = (long)N;
         Rr_.p = nprow_; Rr_.q = myrow_; Cc_.p = npcol_; Cc_.q = mycol_;
@@ -193,7 +200,7 @@ public:
         if (uplo == 'u') uplo = 'U';
         if (uplo == 'l') uplo = 'L';
         if (uplo != 'U' && uplo != 'L') throw std::invalid_argument("symOrHermMatrix: uplo must be 'U' or 'L'");
-        flush_swaps(); sync_comm(); hv_valid_ = false;
+        flush_swaps(); sync_comm(); hv_valid_ = false; hs_valid_ = false;
         hip_ok(chase_hip_tri_mask_bc(ctx_, CP, uplo, (int)m_, (int)n_, dH_, (long)ldh_, Rr_.nb, nprow_, myrow_, Cc_.nb, npcol_, mycol_),
                "tri_mask_bc");
         // ---- index sets (host arithmetic over the local indices) ------------------------------------------------------------
@@ -293,7 +300,18 @@ public:
     std::size_t hemm_calls() const override { return hemm_calls_; }
     std::size_t hemm_reused_vecs() const override { return hemm_reused_vecs_; }
     void set_device_rng(bool f) override { device_rng_ = f; }
-    void reset_counters() override { filter_ms_ = 0; hemm_calls_ = 0; hemm_reused_vecs_ = 0; }
+    void reset_counters() override
+    {
+        filter_ms_ = 0; hemm_calls_ = 0; hemm_reused_vecs_ = 0;
+        hemm_sp_calls_ = 0; hemm_sp_vecs_ = 0; sp_filters_ = 0;
+    }
+    // mixed-precision filter.  Collective: every rank must hold the same value when a filter call starts (the decision in
+    // Shift is taken from the replicated residuals, so equal switches give equal decisions)
+    bool set_mixed_precision(bool on) override { mixed_ = on; return true; }
+    bool mixed_precision() const override { return mixed_; }
+    std::size_t hemm_sp_calls() const override { return hemm_sp_calls_; }
+    std::size_t hemm_sp_vecs() const override { return hemm_sp_vecs_; }
+    std::size_t sp_filters() const override { return sp_filters_; }
     void* device_V1() override { flush_swaps(); sync_comm(); return dV1_; }
     std::size_t local_rows() const override { return m_; }
     std::size_t local_cols_h() const { return n_; }
@@ -316,7 +334,8 @@ public:
     double last_ortho_check() const { return last_ortho_; }          // CHASE_QR_CHECK_ORTHO: ||Q^H Q - I||_inf of the last Householder QR
 
     // ---- life cycle ----------------------------------------------------------------------------------------------------
-    void Start() override { locked_ = 0; }
+    // (the caller owns H_loc and may have changed it between the solves of a sequence: the fp32 shadow is converted anew)
+    void Start() override { locked_ = 0; sp_active_ = false; hs_valid_ = false; }
 
     // pchase_cpu.hpp:272-311: every grid row seeds mt19937(1337 + coords[0]) and fills its block in memory order
     void initVecs(bool random) override
@@ -397,6 +416,54 @@ public:
         if (isunshift) next_bAc_ = true;
         hip_ok(chase_hip_shift_list(ctx_, CP, dH_, (long)ldh_, d_diag_rows_, d_diag_cols_, (int)diag_cnt_, std::real(c)),
                "shift_list");
+        // mixed precision: decided once per filter call like ChaseHip::Shift, from the residuals the driver left in resid_ -
+        // replicated, so every rank decides alike
+        if (isunshift) {
+            sp_active_ = false;
+        } else if (mixed_ && locked_ < nev_ &&
+                   *std::min_element(resid_.begin() + locked_, resid_.begin() + nev_) > (R)1e-3) {
+            begin_single_precision();
+        }
+    }
+    // a qualifying Shift(-c): the fp32 shadow of the (already shifted) local block.  First time after Start(): the whole block;
+    // later filter calls of the solve only changed the diagonal, which is copied from the fp64 block (bitwise what converting
+    // the shifted block gives)
+    void begin_single_precision()
+    {
+        if (!sH_) {
+            auto pad4 = [](std::size_t r) { return std::max<std::size_t>(4, (r + 3) & ~(std::size_t)3); };   // 16-byte columns
+            ld_sh_ = pad4(m_);
+            ld_sx_ = pad4(std::max(m_, n_));
+            alloc((void**)&sH_, ld_sh_ * std::max<std::size_t>(n_, 1) * sizeof(ST));
+            alloc((void**)&sX_, ld_sx_ * nc_ * sizeof(ST));
+        }
+        if (!hs_valid_) {
+            hip_ok(chase_hip_convert_d2s(ctx_, CP, (int)m_, (int)n_, dH_, (long)ldh_, sH_, (long)ld_sh_), "convert_d2s H");
+            hs_valid_ = true;
+        } else {
+            hip_ok(chase_hip_diag_list_d2s(ctx_, CP, dH_, (long)ldh_, sH_, (long)ld_sh_, d_diag_rows_, d_diag_cols_, (int)diag_cnt_),
+                   "diag_list_d2s");
+        }
+        sp_active_ = true;
+        sp_counted_ = false;
+    }
+    // one panel of a filter product on fp32 operands: the input panel is rounded into its columns of the staging block (on the
+    // compute stream, after the panel's event wait: the pipeline's ordering is untouched), the product leaves the kernel in fp64
+    void product_sp(bool bAc, std::size_t c, std::size_t w, T alpha, const T* in, std::size_t in_ld, T beta, T* out, std::size_t out_ld)
+    {
+        const std::size_t rows_in = bAc ? m_ : n_, rows_out = bAc ? n_ : m_;
+        ST* x = sX_ + c * ld_sx_;
+        hip_ok(chase_hip_convert_d2s(ctx_, CP, (int)rows_in, (int)w, in, (long)in_ld, x, (long)ld_sx_), "convert_d2s panel");
+        int rc;
+        if constexpr (is_cplx<T>::value) {
+            const double a[2] = {alpha.real(), alpha.imag()}, b[2] = {beta.real(), beta.imag()};
+            rc = chase_hip_gemm_cz(ctx_, bAc ? 'C' : 'N', (int)rows_out, (int)w, (int)rows_in, a, sH_, (long)ld_sh_, x, (long)ld_sx_, b,
+                                   out, (long)out_ld);
+        } else {
+            rc = chase_hip_gemm_sd(ctx_, bAc ? 'C' : 'N', (int)rows_out, (int)w, (int)rows_in, alpha, sH_, (long)ld_sh_, x,
+                                   (long)ld_sx_, beta, out, (long)out_ld);
+        }
+        hip_ok(rc, "gemm32w");
     }
 
     void HEMM(std::size_t block, T alpha, T beta, std::size_t offset_left, std::size_t offset_right = 0) override
@@ -421,8 +488,15 @@ public:
                 hip_ok(chase_hip_scale_rows(ctx_, CP, (int)n_, (int)ncols, w1, (long)n_, 0, std::real(alpha)), "scale");
                 hemm_reused_vecs_ += ncols;
             } else {
-                hemm_dir(next_bAc_, c0, ncols, alpha, beta, true);
-                ++hemm_calls_;
+                // (the shortcut above, when it applies, has run in fp64 and is no fp32 product)
+                hemm_dir(next_bAc_, c0, ncols, alpha, beta, true, sp_active_);
+                if (sp_active_) {
+                    if (!sp_counted_) { ++sp_filters_; sp_counted_ = true; }
+                    ++hemm_sp_calls_;
+                    hemm_sp_vecs_ += ncols;
+                } else {
+                    ++hemm_calls_;
+                }
             }
         }
         hv_valid_ = false;
@@ -773,15 +847,17 @@ protected:
     // one direction of the distributed HEMM on columns [c0, c0 + nc)  (mpi/hemm.hpp:114-229)
     //   bAc:  W1 = alpha * H_loc^H * V1 + beta' * W1,  beta' = beta on grid row 0 only,  all-reduce over the column group
     //   cAb:  V1 = alpha * H_loc   * W1 + beta' * V1,  beta' = beta on grid col 0 only,  all-reduce over the row group
-    void hemm_dir(bool bAc, std::size_t c0, std::size_t nc, T alpha, T beta, bool pipelined)
+    void hemm_dir(bool bAc, std::size_t c0, std::size_t nc, T alpha, T beta, bool pipelined, bool sp = false)
     {
-        hemm_ptr(bAc, bAc ? dV1_ : dW1_, bAc ? dW1_ : dV1_, c0, nc, alpha, beta, pipelined);
+        hemm_ptr(bAc, bAc ? dV1_ : dW1_, bAc ? dW1_ : dV1_, c0, nc, alpha, beta, pipelined, sp);
     }
     // in: column-type (bAc) / row-type (cAb) block, out: the other type.  bAc multiplies with dHbac_: H_loc itself for a
     // Hermitian matrix; the pseudo-Hermitian Impl points it at G_loc = S H_loc S (signs of the two off-diagonal quadrants
     // flipped), because H V = S H^H S V (mpi/hemm.hpp:125-199) = G^H V — the reference's four vector sign flips around
     // the conj-transposed GEMM are folded into the matrix once, and the panel pipeline applies unchanged.  cAb is H W.
-    void hemm_ptr(bool bAc, T* in, T* out, std::size_t c0, std::size_t nc, T alpha, T beta, bool pipelined)
+    // sp (the Hermitian filter while a mixed-precision filter call runs): the local products multiply the fp32 shadow of H_loc
+    // with the fp32-rounded input panel and write fp64 - everything else, the all-reduces included, is as without it.
+    void hemm_ptr(bool bAc, T* in, T* out, std::size_t c0, std::size_t nc, T alpha, T beta, bool pipelined, bool sp = false)
     {
         const int group = bAc ? CHASE_HIP_COL : CHASE_HIP_ROW;
         const bool root = bAc ? (myrow_ == 0) : (mycol_ == 0);
@@ -812,10 +888,12 @@ protected:
         // the ordering itself lives in panel_pipeline.hpp (and is checked on the CPU against a simulator of streams and events)
         struct Ops {
             pChaseHip* k; bool bAc; int group; T alpha, b; const T* Hb; std::size_t ldb; T* in; std::size_t in_ld; T* out; std::size_t out_ld;
+            bool sp;
             void event_wait(int slot) { coll(chase_hip_grid_event_wait(k->grid_, slot)); }
             void product(std::size_t c, std::size_t w)
             {
-                if (bAc) k->gemm('C', k->n_, w, k->m_, alpha, Hb, ldb, in + c * in_ld, in_ld, b, out + c * out_ld, out_ld);
+                if (sp)       k->product_sp(bAc, c, w, alpha, in + c * in_ld, in_ld, b, out + c * out_ld, out_ld);
+                else if (bAc) k->gemm('C', k->n_, w, k->m_, alpha, Hb, ldb, in + c * in_ld, in_ld, b, out + c * out_ld, out_ld);
                 else     k->gemm('N', k->m_, w, k->n_, alpha, Hb, ldb, in + c * in_ld, in_ld, b, out + c * out_ld, out_ld);
             }
             void allreduce(std::size_t c, std::size_t w, bool async)
@@ -823,7 +901,7 @@ protected:
                 coll(chase_hip_grid_allreduce(k->grid_, group, out + c * out_ld, out_ld * w * E, async ? 1 : 0));
             }
             void event_record(int grp, int slot) { coll(chase_hip_grid_event_record_on(k->grid_, grp, slot)); }
-        } ops{this, bAc, group, alpha, b, Hb, ldb, in, in_ld, out, out_ld};
+        } ops{this, bAc, group, alpha, b, Hb, ldb, in, in_ld, out, out_ld, sp};
         pipelined_product(ops, pipe, active, group, c0, nc, panel_);
     }
     // X <- S X on the local rows of a column-type / row-type block (global rows >= N/2 change sign)
@@ -1119,6 +1197,11 @@ protected:
     std::vector<void*> owned_;
     double filter_ms_ = 0;
     std::size_t hemm_calls_ = 0;
+    // mixed precision: fp32 shadow of H_loc and the staging block of the input panels (allocated on the first qualifying filter
+    // call), their state and counters
+    bool mixed_ = false, sp_active_ = false, sp_counted_ = false, hs_valid_ = false;
+    ST *sH_ = nullptr, *sX_ = nullptr;
+    std::size_t ld_sh_ = 0, ld_sx_ = 0, hemm_sp_calls_ = 0, hemm_sp_vecs_ = 0, sp_filters_ = 0;
     int last_qr_variant_ = 0;
 };
 

@@ -33,6 +33,8 @@ public:
     {
         if (N % 2) throw std::invalid_argument("pChaseHipPseudo: N must be even (2 x 2 block structure)");
         this->pseudo_ = true;
+        this->mixed_ = false;                                             // the H^2 filter runs in fp64
+        mixed_precision_env_ignored("the pseudo-Hermitian grid solver");
         this->alloc((void**)&dG_, this->m_ * this->n_ * sizeof(T));       // S H_loc S, rebuilt from H_loc at every initVecs
         this->dHbac_ = dG_; this->ldhbac_ = this->m_;
         build_g();
@@ -40,6 +42,7 @@ public:
         build_kconj_exchange();
     }
 
+    bool set_mixed_precision(bool on) override { return !on; }
     bool isSym() override { return false; }
     bool isPseudoHerm() override { return true; }
     bool checkSymmetryEasy() override { return false; }

@@ -205,8 +205,8 @@ int chase_hip_solver_set(chase_hip_solver* s, const char* key, double v)
         else if (name == "pipeline" && (s->pd || s->pz)) { if (s->pz) s->pz->set_pipeline(v != 0); else s->pd->set_pipeline(v != 0); }
         else if (name == "mixed_precision") {
             if (!s->ex->set_mixed_precision(v != 0))
-                rc = chase_hip::set_error(CHASE_HIP_EINVAL, "solver_set: mixed_precision exists on the single-GPU Hermitian solver "
-                                                            "only (grid and pseudo-Hermitian solvers filter in fp64)");
+                rc = chase_hip::set_error(CHASE_HIP_EINVAL, "solver_set: mixed_precision exists on the Hermitian solvers only, "
+                                                            "single GPU and grid (the pseudo-Hermitian solvers filter in fp64)");
         }
         else if (name == "reset_counters") s->ex->reset_counters();
         else rc = chase_hip::set_error(CHASE_HIP_EINVAL, "solver_set: unknown key");

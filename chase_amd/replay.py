@@ -167,6 +167,7 @@ def replay_rank(ctx, tape, meta, nprow, npcol, rank=0, block_cyclic=None, oplog=
            "qr_shifted_refactorisations_on_replayed_numbers": int(s.get("tape_qr_retries")),
            "projected_matrices_replaced_by_the_identity": int(s.get("tape_tolerated")),
            "residuals_rechecked": int(s.get("resd_rechecked")),
+           "mixed_precision": int(s.get("mixed_precision")), "filtered_vecs_in_fp32": int(s.get("hemm_sp_vecs")),
            "waits_on_communication_streams": int(waits), "exposed_ms_of_those_waits_with_nothing_on_the_wire": exposed_ms,
            "gemm_books": books, "per_iteration": per_iter,
            "comm_streams": grid.comm_streams(),

@@ -89,6 +89,16 @@ int chase_hip_gemm_s(chase_hip_ctx* ctx, char opA, int m, int n, int k, float al
                      long ldb, float beta, float* C, long ldc);
 int chase_hip_gemm_c(chase_hip_ctx* ctx, char opA, int m, int n, int k, const float alpha[2], const void* A, long lda,
                      const void* B, long ldb, const float beta[2], void* C, long ldc);
+/* The fp32-input product with an fp64 result: C64 = alpha op(A32) B32 + beta C64, A and B real fp32 / interleaved complex fp32,
+ * C, alpha and beta fp64.  opA is 'N' or 'C' (real: 'T' as well; anything else: CHASE_HIP_EINVAL); A is m x k for 'N' (lda >= m)
+ * and k x m for 'C' (lda >= k).  The accumulation over the whole K runs on the f32-input matrix cores exactly as in gemm_s / _c;
+ * alpha acc + beta C is formed in fp64.  This is the filter product of the grid solver: the ranks' partial products are summed
+ * in fp64 by the collectives of the fp64 path.  Bitwise reproducible; beta == 0: C is not read; k == 0 gives beta C; not counted
+ * by chase_hip_ctx_gemm_counters; launches in phase 1 carry a kernel symbol of their own. */
+int chase_hip_gemm_sd(chase_hip_ctx* ctx, char opA, int m, int n, int k, double alpha, const float* A, long lda, const float* B,
+                      long ldb, double beta, double* C, long ldc);
+int chase_hip_gemm_cz(chase_hip_ctx* ctx, char opA, int m, int n, int k, const double alpha[2], const void* A, long lda,
+                      const void* B, long ldb, const double beta[2], void* C, long ldc);
 
 /* bytes of workspace a product of this shape uses on a device with num_cu compute units (context-owned, grown on
  * demand; min_rounds as in chase_hip_ctx_set_gemm_min_rounds): the split-K slabs and - complex products while the
@@ -226,6 +236,10 @@ int chase_hip_lacpy(chase_hip_ctx* ctx, int cplx, int m, int n, const void* A, l
 int chase_hip_convert_d2s(chase_hip_ctx* ctx, int cplx, int m, int n, const void* src, long ld_src, void* dst, long ld_dst);
 int chase_hip_convert_s2d(chase_hip_ctx* ctx, int cplx, int m, int n, const void* src, long ld_src, void* dst, long ld_dst);
 int chase_hip_diag_d2s(chase_hip_ctx* ctx, int cplx, int n, const void* H, long ldh, void* Hs, long ldhs);
+/* the list form of diag_d2s: Hs[rows[i], cols[i]] = (fp32) H[rows[i], cols[i]] for i < cnt, nothing else of Hs is touched; rows
+ * and cols are DEVICE int arrays (the lists chase_hip_shift_list takes: the global diagonal inside a rank's block) */
+int chase_hip_diag_list_d2s(chase_hip_ctx* ctx, int cplx, const void* H, long ldh, void* Hs, long ldhs, const int* rows_dev,
+                            const int* cols_dev, int cnt);
 /* swap columns i and j of V.  Replaces chase_gpu.hpp:1003-1005 (cublasTswap) */
 int chase_hip_swap_cols(chase_hip_ctx* ctx, int cplx, int m, void* V, long ldv, long i, long j);
 /* apply a batch of deferred Swap()s: V[:, dst[c]] <- V[:, src[c]] simultaneously; src/dst are host arrays, scratch is a

@@ -58,10 +58,11 @@ int chase_hip_solver_destroy(chase_hip_solver* s);
  * from the layout's largest local block, but at most 1 / 2.5 of nev + nex and not below 128 - a product must consist of several
  * panels for any of its all-reduce to hide), panel_rounds (K pieces of a panel product that shares the chip with a collective,
  * 0..16, default 4 = CHASE_HIP_PANEL_ROUNDS), pipeline (0: every all-reduce waited for where it is issued).
- * mixed_precision (set and get, 0 | 1, default 0 or CHASE_HIP_MIXED_PRECISION at construction; single-GPU Hermitian Impl only -
- * setting 1 on a grid or pseudo-Hermitian solver returns CHASE_HIP_EINVAL): the reference's CHASE_ENABLE_MIXED_PRECISION rule - a
- * filter call that starts while the smallest residual of the unlocked wanted pairs is above 1e-3 runs its products in fp32 on
- * shadow copies of H and the vectors.  get additionally: hemm_sp_calls (fp32 products), hemm_sp_vecs (columns filtered in fp32),
+ * mixed_precision (set and get, 0 | 1, default 0 or CHASE_HIP_MIXED_PRECISION at construction; the Hermitian Impls, single GPU and
+ * grid - setting 1 on a pseudo-Hermitian solver returns CHASE_HIP_EINVAL; on a grid COLLECTIVE like the knobs above): the
+ * reference's CHASE_ENABLE_MIXED_PRECISION rule - a filter call that starts while the smallest residual of the unlocked wanted
+ * pairs is above 1e-3 runs its products in fp32: on one GPU on shadow copies of H and the vectors, on a grid on a shadow of the
+ * local block and the rounded input panel, every rank's partial product written and summed in fp64.  get additionally: hemm_sp_calls (fp32 products), hemm_sp_vecs (columns filtered in fp32),
  * sp_filters (filter calls that ran in fp32); reset_counters clears them. */
 int chase_hip_solver_set(chase_hip_solver* s, const char* key, double value);
 int chase_hip_solver_get(chase_hip_solver* s, const char* key, double* value);
