@@ -75,6 +75,8 @@ _sig("chase_hip_gemm_sd", c_int, c_void_p, c_char, c_int, c_int, c_int, c_double
      c_double, c_void_p, c_long)
 _sig("chase_hip_gemm_cz", c_int, c_void_p, c_char, c_int, c_int, c_int, P(c_double), c_void_p, c_long, c_void_p,
      c_long, P(c_double), c_void_p, c_long)
+for _n in ("s", "c", "sd", "cz"):          # the split-operand (bf16x3) forms have the signatures of the fp32 MFMA ones
+    _sig("chase_hip_gemm_%s_bf16x3" % _n, c_int, *getattr(lib, "chase_hip_gemm_" + _n).argtypes)
 _sig("chase_hip_diag_list_d2s", c_int, c_void_p, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_int)
 _sig("chase_hip_convert_d2s", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
 _sig("chase_hip_convert_s2d", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
@@ -209,21 +211,27 @@ class Context:
             check(lib.chase_hip_gemm_d(self.h, op, m, n, k, float(alpha), A, lda, B, ldb, float(beta), Cm, ldc),
                   "gemm_d")
 
-    def gemm32(self, opA, m, n, k, alpha, A, lda, B, ldb, beta, Cm, ldc, cplx):
-        """Single-precision GEMM (fp32 / complex fp32, op(A) = N only): A, B, Cm are device addresses (ints)."""
+    def gemm32(self, opA, m, n, k, alpha, A, lda, B, ldb, beta, Cm, ldc, cplx, split=False):
+        """Single-precision GEMM (fp32 / complex fp32, op(A) = N only): A, B, Cm are device addresses (ints).
+        split: the bf16x3 product on the bf16 matrix cores instead of the fp32 MFMA one."""
         op = opA.encode()[0:1]
         if cplx:
-            check(lib.chase_hip_gemm_c(self.h, op, m, n, k, _c2(alpha), A, lda, B, ldb, _c2(beta), Cm, ldc), "gemm_c")
+            f = lib.chase_hip_gemm_c_bf16x3 if split else lib.chase_hip_gemm_c
+            check(f(self.h, op, m, n, k, _c2(alpha), A, lda, B, ldb, _c2(beta), Cm, ldc), "gemm_c")
         else:
-            check(lib.chase_hip_gemm_s(self.h, op, m, n, k, float(alpha), A, lda, B, ldb, float(beta), Cm, ldc), "gemm_s")
+            f = lib.chase_hip_gemm_s_bf16x3 if split else lib.chase_hip_gemm_s
+            check(f(self.h, op, m, n, k, float(alpha), A, lda, B, ldb, float(beta), Cm, ldc), "gemm_s")
 
-    def gemm32w(self, opA, m, n, k, alpha, A, lda, B, ldb, beta, Cm, ldc, cplx):
-        """fp32 operands, fp64 result and scalars, op(A) = N or C (the grid filter's product): device addresses (ints)."""
+    def gemm32w(self, opA, m, n, k, alpha, A, lda, B, ldb, beta, Cm, ldc, cplx, split=False):
+        """fp32 operands, fp64 result and scalars, op(A) = N or C (the grid filter's product): device addresses (ints).
+        split: as in gemm32."""
         op = opA.encode()[0:1]
         if cplx:
-            check(lib.chase_hip_gemm_cz(self.h, op, m, n, k, _z2(alpha), A, lda, B, ldb, _z2(beta), Cm, ldc), "gemm_cz")
+            f = lib.chase_hip_gemm_cz_bf16x3 if split else lib.chase_hip_gemm_cz
+            check(f(self.h, op, m, n, k, _z2(alpha), A, lda, B, ldb, _z2(beta), Cm, ldc), "gemm_cz")
         else:
-            check(lib.chase_hip_gemm_sd(self.h, op, m, n, k, float(alpha), A, lda, B, ldb, float(beta), Cm, ldc), "gemm_sd")
+            f = lib.chase_hip_gemm_sd_bf16x3 if split else lib.chase_hip_gemm_sd
+            check(f(self.h, op, m, n, k, float(alpha), A, lda, B, ldb, float(beta), Cm, ldc), "gemm_sd")
 
     def diag_list_d2s(self, H, ldh, Hs, ldhs, rows, cols, cnt, cplx):
         """Hs[rows[i], cols[i]] (fp32) = H[rows[i], cols[i]] (fp64), i < cnt; rows, cols: device addresses of int32 lists."""

@@ -254,18 +254,20 @@ int chase_hip_gemm_z(chase_hip_ctx* c, char opA, int m, int n, int k, const doub
     return c->gemm(true, opA, m, n, k, alpha, (const double*)A, lda, (const double*)B, ldb, beta, (double*)C, ldc);
 }
 
+// split: the bf16x3 product (gemm_mfma_bf16x3.hip) instead of the fp32 MFMA one
 static int gemm32(chase_hip_ctx* c, bool cplx, char opA, int m, int n, int k, const float* alpha, const float* A, long lda,
-                  const float* B, long ldb, const float* beta, float* C, long ldc)
+                  const float* B, long ldb, const float* beta, float* C, long ldc, bool split = false)
 {
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     if (opA != 'N' && opA != 'n')
         return set_error(CHASE_HIP_EINVAL, "gemm_s / gemm_c: opA must be 'N' (the single-precision product is the filter's)");
     int rc = check_gemm(opA, m, n, k, A, lda, B, ldb, C, ldc);
     if (rc || m == 0 || n == 0) return rc;
-    if (c->oplog_on) c->oplog_add(cplx ? "gemm_cN" : "gemm_sN", m, n, k, c->phase * 100);
-    int e = gemm_f32(c->stream, cplx, opA, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, c->num_cu, c->phase == 1 ? 1 : 0);
+    if (c->oplog_on) c->oplog_add(split ? (cplx ? "gemm_c3N" : "gemm_s3N") : (cplx ? "gemm_cN" : "gemm_sN"), m, n, k, c->phase * 100);
+    int e = (split ? gemm_bf16x3 : gemm_f32)(c->stream, cplx, opA, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, c->num_cu,
+                                             c->phase == 1 ? 1 : 0);
     if (e == GEMM_F32_EOP) return set_error(CHASE_HIP_EINVAL, "gemm_s / gemm_c: opA must be 'N'");
-    if (e) return hip_fail((hipError_t)e, "gemm_f32 launch");
+    if (e) return hip_fail((hipError_t)e, split ? "gemm_bf16x3 launch" : "gemm_f32 launch");
     return 0;
 }
 
@@ -284,9 +286,24 @@ int chase_hip_gemm_c(chase_hip_ctx* c, char opA, int m, int n, int k, const floa
     return gemm32(c, true, opA, m, n, k, alpha, (const float*)A, lda, (const float*)B, ldb, beta, (float*)C, ldc);
 }
 
+int chase_hip_gemm_s_bf16x3(chase_hip_ctx* c, char opA, int m, int n, int k, float alpha, const float* A, long lda, const float* B,
+                            long ldb, float beta, float* C, long ldc)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "ctx == NULL");
+    return gemm32(c, false, opA, m, n, k, &alpha, A, lda, B, ldb, &beta, C, ldc, true);
+}
+
+int chase_hip_gemm_c_bf16x3(chase_hip_ctx* c, char opA, int m, int n, int k, const float alpha[2], const void* A, long lda,
+                            const void* B, long ldb, const float beta[2], void* C, long ldc)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "ctx == NULL");
+    if (!alpha || !beta) return set_error(CHASE_HIP_EINVAL, "gemm_c: NULL alpha/beta");
+    return gemm32(c, true, opA, m, n, k, alpha, (const float*)A, lda, (const float*)B, ldb, beta, (float*)C, ldc, true);
+}
+
 // fp32 operands, fp64 result and scalars, op(A) = N or C: the filter product of the grid solver
 static int gemm32w(chase_hip_ctx* c, bool cplx, char opA, int m, int n, int k, const double* alpha, const float* A, long lda,
-                   const float* B, long ldb, const double* beta, double* C, long ldc)
+                   const float* B, long ldb, const double* beta, double* C, long ldc, bool split = false)
 {
     (void)hipSetDevice(c->device);      // entry points may be called with another device current
     const bool opn = opA == 'N' || opA == 'n';
@@ -295,10 +312,15 @@ static int gemm32w(chase_hip_ctx* c, bool cplx, char opA, int m, int n, int k, c
         return set_error(CHASE_HIP_EINVAL, cplx ? "gemm_cz: opA must be 'N' or 'C'" : "gemm_sd: opA must be 'N', 'C' or 'T'");
     int rc = check_gemm(opA, m, n, k, A, lda, B, ldb, C, ldc);
     if (rc || m == 0 || n == 0) return rc;
-    if (c->oplog_on) c->oplog_add(cplx ? (opn ? "gemm_czN" : "gemm_czC") : (opn ? "gemm_sdN" : "gemm_sdC"), m, n, k, c->phase * 100);
-    int e = gemm_f32w(c->stream, cplx, opA, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, c->num_cu, c->phase == 1 ? 1 : 0);
+    if (c->oplog_on) {
+        const char* name = split ? (cplx ? (opn ? "gemm_cz3N" : "gemm_cz3C") : (opn ? "gemm_sd3N" : "gemm_sd3C"))
+                                 : (cplx ? (opn ? "gemm_czN" : "gemm_czC") : (opn ? "gemm_sdN" : "gemm_sdC"));
+        c->oplog_add(name, m, n, k, c->phase * 100);
+    }
+    int e = (split ? gemm_bf16x3w : gemm_f32w)(c->stream, cplx, opA, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, c->num_cu,
+                                               c->phase == 1 ? 1 : 0);
     if (e == GEMM_F32_EOP) return set_error(CHASE_HIP_EINVAL, "gemm_sd / gemm_cz: bad opA");
-    if (e) return hip_fail((hipError_t)e, "gemm_f32w launch");
+    if (e) return hip_fail((hipError_t)e, split ? "gemm_bf16x3w launch" : "gemm_f32w launch");
     return 0;
 }
 
@@ -315,6 +337,21 @@ int chase_hip_gemm_cz(chase_hip_ctx* c, char opA, int m, int n, int k, const dou
     if (!c) return set_error(CHASE_HIP_EINVAL, "ctx == NULL");
     if (!alpha || !beta) return set_error(CHASE_HIP_EINVAL, "gemm_cz: NULL alpha/beta");
     return gemm32w(c, true, opA, m, n, k, alpha, (const float*)A, lda, (const float*)B, ldb, beta, (double*)C, ldc);
+}
+
+int chase_hip_gemm_sd_bf16x3(chase_hip_ctx* c, char opA, int m, int n, int k, double alpha, const float* A, long lda, const float* B,
+                             long ldb, double beta, double* C, long ldc)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "ctx == NULL");
+    return gemm32w(c, false, opA, m, n, k, &alpha, A, lda, B, ldb, &beta, C, ldc, true);
+}
+
+int chase_hip_gemm_cz_bf16x3(chase_hip_ctx* c, char opA, int m, int n, int k, const double alpha[2], const void* A, long lda,
+                             const void* B, long ldb, const double beta[2], void* C, long ldc)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "ctx == NULL");
+    if (!alpha || !beta) return set_error(CHASE_HIP_EINVAL, "gemm_cz: NULL alpha/beta");
+    return gemm32w(c, true, opA, m, n, k, alpha, (const float*)A, lda, (const float*)B, ldb, beta, (double*)C, ldc, true);
 }
 
 /* bytes of split-K workspace chase_hip_gemm_{d,z} uses for this shape on a device with num_cu compute units (a pure function

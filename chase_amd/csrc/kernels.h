@@ -40,6 +40,12 @@ int gemm_f32(hipStream_t st, bool cplx, char opA, int m, int n, int k, const flo
 // of the ranks are summed in fp64.
 int gemm_f32w(hipStream_t st, bool cplx, char opA, int m, int n, int k, const double* alpha, const float* A, long lda,
               const float* B, long ldb, const double* beta, double* C, long ldc, int num_cu, int tag = 0);
+// the same two products on the bf16 matrix cores with every fp32 operand split into three bf16 parts in the kernel
+// (gemm_mfma_bf16x3.hip): six partial products per k in the fp32 accumulator.  Interfaces, statuses and reproducibility as above.
+int gemm_bf16x3(hipStream_t st, bool cplx, char opA, int m, int n, int k, const float* alpha, const float* A, long lda, const float* B,
+                long ldb, const float* beta, float* C, long ldc, int num_cu, int tag = 0);
+int gemm_bf16x3w(hipStream_t st, bool cplx, char opA, int m, int n, int k, const double* alpha, const float* A, long lda,
+                 const float* B, long ldb, const double* beta, double* C, long ldc, int num_cu, int tag = 0);
 
 int mfma_f64_peak(hipStream_t st, double* out, int blocks, int iters);
 int stream_copy(hipStream_t st, void* dst, const void* src, size_t bytes);

@@ -73,6 +73,7 @@ public:
         alloc((void**)&dA_, nevex_ * nevex_ * sizeof(T));
         alloc((void**)&dScal_, 4096);
         if (const char* e = std::getenv("CHASE_HIP_MIXED_PRECISION")) mixed_ = std::atoi(e) != 0;
+        sp_split_ = sp_product_env() != 0;
     }
     ~ChaseHip() override
     {
@@ -223,7 +224,7 @@ public:
     void reset_counters() override
     {
         filter_ms_ = 0; hemm_calls_ = 0; hemm_reused_vecs_ = 0;
-        hemm_sp_calls_ = 0; hemm_sp_vecs_ = 0; sp_filters_ = 0;
+        hemm_sp_calls_ = 0; hemm_sp_vecs_ = 0; sp_filters_ = 0; hemm_sp_split_calls_ = 0;
     }
     std::size_t hemm_calls() const override { return hemm_calls_; }
     std::size_t hemm_reused_vecs() const override { return hemm_reused_vecs_; }
@@ -232,6 +233,9 @@ public:
     std::size_t hemm_sp_calls() const override { return hemm_sp_calls_; }
     std::size_t hemm_sp_vecs() const override { return hemm_sp_vecs_; }
     std::size_t sp_filters() const override { return sp_filters_; }
+    bool set_sp_product(int v) override { sp_split_ = v != 0; return true; }
+    int sp_product() const override { return sp_split_ ? 1 : 0; }
+    std::size_t hemm_sp_split_calls() const override { return hemm_sp_split_calls_; }
 
     // The filter brackets its products with Shift(-c) ... Shift(+c, true).  Mixed precision (chase_cpu.hpp:384-445): the decision
     // is taken here, once per filter call, from the residuals the driver left in resid_ (all max() before the first iteration).
@@ -284,6 +288,7 @@ public:
                 gemm32(N_, ncols, N_, alpha, sH_, ld_s_, sV1_ + c0 * ld_s_, ld_s_, beta, sV2_ + c0 * ld_s_, ld_s_);
                 ++hemm_sp_calls_;
                 hemm_sp_vecs_ += ncols;
+                if (sp_split_) ++hemm_sp_split_calls_;
             } else {
                 gemm('N', N_, ncols, N_, alpha, dH_, ldd_h_, dV1_ + c0 * N_, N_, beta, dV2_ + c0 * N_, N_);
                 ++hemm_calls_;
@@ -521,9 +526,11 @@ private:
         int rc;
         if constexpr (is_cplx<T>::value) {
             const float a[2] = {(float)alpha.real(), (float)alpha.imag()}, b[2] = {(float)beta.real(), (float)beta.imag()};
-            rc = chase_hip_gemm_c(ctx_, 'N', (int)m, (int)n, (int)k, a, A, (long)lda, B, (long)ldb, b, C, (long)ldc);
+            rc = (sp_split_ ? chase_hip_gemm_c_bf16x3 : chase_hip_gemm_c)(ctx_, 'N', (int)m, (int)n, (int)k, a, A, (long)lda, B, (long)ldb,
+                                                                          b, C, (long)ldc);
         } else {
-            rc = chase_hip_gemm_s(ctx_, 'N', (int)m, (int)n, (int)k, (float)alpha, A, (long)lda, B, (long)ldb, (float)beta, C, (long)ldc);
+            rc = (sp_split_ ? chase_hip_gemm_s_bf16x3 : chase_hip_gemm_s)(ctx_, 'N', (int)m, (int)n, (int)k, (float)alpha, A, (long)lda, B,
+                                                                          (long)ldb, (float)beta, C, (long)ldc);
         }
         hip_ok(rc, "gemm32");
     }
@@ -660,7 +667,8 @@ private:
     // mixed precision: fp32 shadows (allocated on the first qualifying filter call), their state and counters
     bool mixed_ = false, sp_active_ = false, sp_synced_ = false, hs_valid_ = false;
     ST *sH_ = nullptr, *sV1_ = nullptr, *sV2_ = nullptr;
-    std::size_t ld_s_ = 0, hemm_sp_calls_ = 0, hemm_sp_vecs_ = 0, sp_filters_ = 0;
+    std::size_t ld_s_ = 0, hemm_sp_calls_ = 0, hemm_sp_vecs_ = 0, sp_filters_ = 0, hemm_sp_split_calls_ = 0;
+    bool sp_split_ = false;                // sp_product = 1: the fp32 filter products run as bf16x3
 };
 
 } // namespace chase_amd

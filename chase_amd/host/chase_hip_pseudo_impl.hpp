@@ -53,6 +53,7 @@ public:
         alloc((void**)&dA_, 3 * nc_ * nc_ * sizeof(T));
         alloc((void**)&dScal_, 4096);
         mixed_precision_env_ignored("the pseudo-Hermitian solver");
+        sp_product_env_ignored("the pseudo-Hermitian solver");
     }
     ~ChaseHipPseudo() override { for (void* p : owned_) chase_hip_free(ctx_, p); }
 

@@ -5,6 +5,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 namespace chase_amd {
 
@@ -23,6 +24,11 @@ struct HipImplExtras {
     virtual std::size_t hemm_sp_calls() const { return 0; }      // fp32 filter products
     virtual std::size_t hemm_sp_vecs() const { return 0; }       // columns filtered in fp32
     virtual std::size_t sp_filters() const { return 0; }         // filter calls that ran in fp32
+    // which product a filter call in single precision uses: 0 = fp32 MFMA (default), 1 = bf16x3 (split operands on the bf16
+    // matrix cores); no effect while mixed_precision is off.  false = this Impl has no fp32 path and v != 0 was not taken
+    virtual bool set_sp_product(int v) { return v == 0; }
+    virtual int sp_product() const { return 0; }
+    virtual std::size_t hemm_sp_split_calls() const { return 0; }   // fp32 filter products that ran as bf16x3
     virtual void set_device_rng(bool) = 0;
     virtual void reset_counters() = 0;
     virtual void* device_V1() = 0;               // current (local) vector block, pending swaps applied
@@ -54,6 +60,19 @@ inline void mixed_precision_env_ignored(const char* impl)
     const char* e = std::getenv("CHASE_HIP_MIXED_PRECISION");
     if (!e || std::atoi(e) == 0 || said.exchange(true)) return;
     std::fprintf(stderr, "chase_hip: CHASE_HIP_MIXED_PRECISION is ignored by %s (Hermitian solvers only)\n", impl);
+}
+
+// CHASE_HIP_SP_PRODUCT=bf16x3|f32: the construction-time default of sp_product (anything else: f32)
+inline int sp_product_env()
+{
+    const char* e = std::getenv("CHASE_HIP_SP_PRODUCT");
+    return e && std::strcmp(e, "bf16x3") == 0 ? 1 : 0;
+}
+inline void sp_product_env_ignored(const char* impl)
+{
+    static std::atomic<bool> said{false};
+    if (sp_product_env() == 0 || said.exchange(true)) return;
+    std::fprintf(stderr, "chase_hip: CHASE_HIP_SP_PRODUCT is ignored by %s (Hermitian solvers only)\n", impl);
 }
 
 } // namespace chase_amd

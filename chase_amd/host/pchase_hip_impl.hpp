@@ -76,6 +76,7 @@ public:
         if (!ctx || !grid || !H_loc || !ritzv) throw std::invalid_argument("pChaseHip: null argument");
         if (N == 0 || nevex_ == 0 || nc_ > N) throw std::invalid_argument("pChaseHip: need 0 < nev+nex <= N");
         if (const char* e = std::getenv("CHASE_HIP_MIXED_PRECISION")) mixed_ = std::atoi(e) != 0;   // (the pseudo Impl clears it)
+        sp_split_ = sp_product_env() != 0;                                                         // (and this)
         hip_ok(chase_hip_grid_info(grid, &nprow_, &npcol_, &myrow_, &mycol_), "grid_info");
         Rr_.N = Cc_.N = (long)N;
         Rr_.p = nprow_; Rr_.q = myrow_; Cc_.p = npcol_; Cc_.q = mycol_;
@@ -303,7 +304,7 @@ public:
     void reset_counters() override
     {
         filter_ms_ = 0; hemm_calls_ = 0; hemm_reused_vecs_ = 0;
-        hemm_sp_calls_ = 0; hemm_sp_vecs_ = 0; sp_filters_ = 0;
+        hemm_sp_calls_ = 0; hemm_sp_vecs_ = 0; sp_filters_ = 0; hemm_sp_split_calls_ = 0;
     }
     // mixed-precision filter.  Collective: every rank must hold the same value when a filter call starts (the decision in
     // Shift is taken from the replicated residuals, so equal switches give equal decisions)
@@ -312,6 +313,9 @@ public:
     std::size_t hemm_sp_calls() const override { return hemm_sp_calls_; }
     std::size_t hemm_sp_vecs() const override { return hemm_sp_vecs_; }
     std::size_t sp_filters() const override { return sp_filters_; }
+    bool set_sp_product(int v) override { sp_split_ = v != 0; return true; }      // collective, like mixed_precision
+    int sp_product() const override { return sp_split_ ? 1 : 0; }
+    std::size_t hemm_sp_split_calls() const override { return hemm_sp_split_calls_; }
     void* device_V1() override { flush_swaps(); sync_comm(); return dV1_; }
     std::size_t local_rows() const override { return m_; }
     std::size_t local_cols_h() const { return n_; }
@@ -457,11 +461,12 @@ public:
         int rc;
         if constexpr (is_cplx<T>::value) {
             const double a[2] = {alpha.real(), alpha.imag()}, b[2] = {beta.real(), beta.imag()};
-            rc = chase_hip_gemm_cz(ctx_, bAc ? 'C' : 'N', (int)rows_out, (int)w, (int)rows_in, a, sH_, (long)ld_sh_, x, (long)ld_sx_, b,
-                                   out, (long)out_ld);
+            rc = (sp_split_ ? chase_hip_gemm_cz_bf16x3 : chase_hip_gemm_cz)(ctx_, bAc ? 'C' : 'N', (int)rows_out, (int)w, (int)rows_in, a,
+                                                                            sH_, (long)ld_sh_, x, (long)ld_sx_, b, out, (long)out_ld);
         } else {
-            rc = chase_hip_gemm_sd(ctx_, bAc ? 'C' : 'N', (int)rows_out, (int)w, (int)rows_in, alpha, sH_, (long)ld_sh_, x,
-                                   (long)ld_sx_, beta, out, (long)out_ld);
+            rc = (sp_split_ ? chase_hip_gemm_sd_bf16x3 : chase_hip_gemm_sd)(ctx_, bAc ? 'C' : 'N', (int)rows_out, (int)w, (int)rows_in,
+                                                                            alpha, sH_, (long)ld_sh_, x, (long)ld_sx_, beta, out,
+                                                                            (long)out_ld);
         }
         hip_ok(rc, "gemm32w");
     }
@@ -494,6 +499,7 @@ public:
                     if (!sp_counted_) { ++sp_filters_; sp_counted_ = true; }
                     ++hemm_sp_calls_;
                     hemm_sp_vecs_ += ncols;
+                    if (sp_split_) ++hemm_sp_split_calls_;
                 } else {
                     ++hemm_calls_;
                 }
@@ -1201,7 +1207,8 @@ protected:
     // call), their state and counters
     bool mixed_ = false, sp_active_ = false, sp_counted_ = false, hs_valid_ = false;
     ST *sH_ = nullptr, *sX_ = nullptr;
-    std::size_t ld_sh_ = 0, ld_sx_ = 0, hemm_sp_calls_ = 0, hemm_sp_vecs_ = 0, sp_filters_ = 0;
+    std::size_t ld_sh_ = 0, ld_sx_ = 0, hemm_sp_calls_ = 0, hemm_sp_vecs_ = 0, sp_filters_ = 0, hemm_sp_split_calls_ = 0;
+    bool sp_split_ = false;                // sp_product = 1: the fp32 filter products run as bf16x3
     int last_qr_variant_ = 0;
 };
 

@@ -35,6 +35,8 @@ public:
         this->pseudo_ = true;
         this->mixed_ = false;                                             // the H^2 filter runs in fp64
         mixed_precision_env_ignored("the pseudo-Hermitian grid solver");
+        this->sp_split_ = false;
+        sp_product_env_ignored("the pseudo-Hermitian grid solver");
         this->alloc((void**)&dG_, this->m_ * this->n_ * sizeof(T));       // S H_loc S, rebuilt from H_loc at every initVecs
         this->dHbac_ = dG_; this->ldhbac_ = this->m_;
         build_g();
@@ -43,6 +45,7 @@ public:
     }
 
     bool set_mixed_precision(bool on) override { return !on; }
+    bool set_sp_product(int v) override { return v == 0; }
     bool isSym() override { return false; }
     bool isPseudoHerm() override { return true; }
     bool checkSymmetryEasy() override { return false; }

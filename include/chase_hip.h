@@ -99,6 +99,20 @@ int chase_hip_gemm_sd(chase_hip_ctx* ctx, char opA, int m, int n, int k, double 
                       long ldb, double beta, double* C, long ldc);
 int chase_hip_gemm_cz(chase_hip_ctx* ctx, char opA, int m, int n, int k, const double alpha[2], const void* A, long lda,
                       const void* B, long ldb, const double beta[2], void* C, long ldc);
+/* The four single-precision products above on the bf16 matrix cores with split operands ("bf16x3"): A and B are the same fp32
+ * arrays; the kernel writes every operand as the exact sum of three bf16 numbers and accumulates the six partial products
+ * a_i b_j, i + j <= 4, in the fp32 accumulator of v_mfma_f32_32x32x16_bf16 - the fp32 product to within u/4 per term, at a
+ * matrix-core ceiling of 16/6 of the f32-input instruction's.  Arguments, checks, statuses, tile order and reproducibility are
+ * those of gemm_s / _c / _sd / _cz; not counted by chase_hip_ctx_gemm_counters; operator-log names gemm_s3N, gemm_c3N,
+ * gemm_sd3N/C, gemm_cz3N/C.  Operands must be finite and below the largest bf16 number (3.39e38) in magnitude. */
+int chase_hip_gemm_s_bf16x3(chase_hip_ctx* ctx, char opA, int m, int n, int k, float alpha, const float* A, long lda,
+                            const float* B, long ldb, float beta, float* C, long ldc);
+int chase_hip_gemm_c_bf16x3(chase_hip_ctx* ctx, char opA, int m, int n, int k, const float alpha[2], const void* A, long lda,
+                            const void* B, long ldb, const float beta[2], void* C, long ldc);
+int chase_hip_gemm_sd_bf16x3(chase_hip_ctx* ctx, char opA, int m, int n, int k, double alpha, const float* A, long lda,
+                             const float* B, long ldb, double beta, double* C, long ldc);
+int chase_hip_gemm_cz_bf16x3(chase_hip_ctx* ctx, char opA, int m, int n, int k, const double alpha[2], const void* A, long lda,
+                             const void* B, long ldb, const double beta[2], void* C, long ldc);
 
 /* bytes of workspace a product of this shape uses on a device with num_cu compute units (context-owned, grown on
  * demand; min_rounds as in chase_hip_ctx_set_gemm_min_rounds): the split-K slabs and - complex products while the

@@ -63,7 +63,13 @@ int chase_hip_solver_destroy(chase_hip_solver* s);
  * reference's CHASE_ENABLE_MIXED_PRECISION rule - a filter call that starts while the smallest residual of the unlocked wanted
  * pairs is above 1e-3 runs its products in fp32: on one GPU on shadow copies of H and the vectors, on a grid on a shadow of the
  * local block and the rounded input panel, every rank's partial product written and summed in fp64.  get additionally: hemm_sp_calls (fp32 products), hemm_sp_vecs (columns filtered in fp32),
- * sp_filters (filter calls that ran in fp32); reset_counters clears them. */
+ * sp_filters (filter calls that ran in fp32); reset_counters clears them.
+ * sp_product (set and get, 0 | 1 - anything else CHASE_HIP_EINVAL; default 0 or CHASE_HIP_SP_PRODUCT=bf16x3|f32 at construction;
+ * COLLECTIVE on a grid; 1 on a pseudo-Hermitian solver returns CHASE_HIP_EINVAL): which product a filter call uses once
+ * mixed_precision has put it into single precision - 0 the fp32 MFMA (chase_hip_gemm_s / _c / _sd / _cz), 1 the bf16x3 split
+ * product on the bf16 matrix cores (chase_hip_gemm_*_bf16x3).  The 1e-3 rule, the shadows, the conversions and the counters above
+ * are untouched, and with mixed_precision = 0 the key has no effect.  get additionally: hemm_sp_split_calls (the hemm_sp_calls
+ * that ran as bf16x3; cleared by reset_counters). */
 int chase_hip_solver_set(chase_hip_solver* s, const char* key, double value);
 int chase_hip_solver_get(chase_hip_solver* s, const char* key, double* value);
 int chase_hip_solver_solve(chase_hip_solver* s, int record_trace);
