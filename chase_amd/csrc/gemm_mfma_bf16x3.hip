@@ -18,10 +18,11 @@
 // Cr += Ar Br + (-Ai) Bi, Ci += Ar Bi + Ai Br, the minus sign being a sign-bit flip of the Ai fragments in registers and the
 // conjugation of op = C a sign flip of the imaginary part before it is split (the split commutes with negation).
 //
-// Launch shape, as in gemm_mfma_f32.hip: one 256-thread workgroup per 128 x BN output tile (real: BN = 128 or 64 by the same
-// tile_cols rule; complex: BN = 64, see LDS) over the WHOLE K - no split-K, no atomics, one fixed summation order per element, bitwise reproducible - in the same
-// XCD-contiguous tile order; four waves of 64 x BN/2 = 2 x WN MFMA tiles.  K step 16 (one MFMA k) for real and complex.  The
-// global loads of step t + 1 are issued in front of the MFMAs of step t and waited for only where they are split and stored.
+// Launch shape: the frame of gemm_sp_frame.h, which also holds the kernel arguments, the tile order, the K pipeline, the
+// tile-width rule and the host setup (the epilogue: gemm_sp_epilogue.h) - one 256-thread workgroup per 128 x BN output tile over the whole K, four
+// waves of 64 x BN/2 = 2 x WN MFMA tiles; real: BN = 128 or 64 by the tile-width rule, complex: BN = 64 (see LDS).  K step 16 (one
+// MFMA k) for real and complex.  The global loads of step t + 1 are issued in front of the MFMAs of step t and waited for only
+// where they are split and stored.
 //
 // LDS.  One plane is [row][16 k] bf16, 32 bytes per row; a 128-row operand has 3 (real) / 6 (complex) planes of 4 KB.  All
 // tiles are double buffered in LDS and run two workgroups per CU, which __launch_bounds__(256, 2) promises (the other
@@ -47,32 +48,17 @@
 //
 // Any m, n, k >= 0 and any leading dimensions: guarded element accesses with zero fill wherever a tile is not whole or an
 // operand not 16-byte addressable.  beta == 0: C is not read.  k == 0: C = beta C.
-#include <hip/hip_runtime.h>
-#include <cstdint>
-#include "kernels.h"
+#include "gemm_sp_frame.h"
 
 namespace chase_hip {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace sp_frame;
+
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int BM = 128;            // tile rows
 constexpr int BK = 16;             // k per step: one MFMA
-
-struct Args {
-    int m, n, k;
-    float ar, ai, br, bi;
-    const float* A; long lda;
-    const float* B; long ldb;
-    float* C; long ldc;
-    double war, wai, wbr, wbi;     // WIDE: fp64 scalars and an fp64 C (ldc in its elements)
-    double* Cw;
-    int gn;                        // tiles along n
-    unsigned total;                // tiles
-    int vecA, vecB, vecC;          // 16-byte accesses allowed (base pointer and leading dimension)
-};
 
 // 16-byte piece (row, h) of a plane, in 16-byte units (the file comment derives the swizzle)
 __device__ __forceinline__ int piece(int row, int h) { return 2 * row + (h ^ (((row >> 2) ^ (row >> 3)) & 1)); }
@@ -107,14 +93,9 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_kernel(const Args a)
     __shared__ u32x4 sA[2][3 * E * PA];
     __shared__ u32x4 sB[2][3 * E * PB];
 
-    // tile id: eight consecutive workgroups land on eight different XCDs (each with an L2 of its own) - give every XCD a
-    // contiguous run of tiles, n fastest, so that the tiles sharing a row block of A meet in one L2
-    unsigned id = blockIdx.x;
-    if ((a.total & 7u) == 0) id = (id & 7u) * (a.total >> 3) + (id >> 3);
-    const int tn = (int)(id % (unsigned)a.gn), tm = (int)(id / (unsigned)a.gn);
-    const long m0 = (long)tm * BM, n0 = (long)tn * BN;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w & 1, wn = w >> 1, lr = lane & 31, lh = lane >> 5;
+    const Place at = place<BN>(a);
+    const long m0 = at.m0, n0 = at.n0;
+    const int tid = at.tid, wm = at.wm, wn = at.wn, lr = at.lr, lh = at.lh;
     const int ja = tid % BM, ha = tid / BM;                    // this thread's piece of the A tile: row, k half
     const int jb = tid % BN, hb = tid / BN;                    // and of the B tile (hb < 2)
     const bool has_b = HB == 2 || hb < 2;                      // wave-uniform
@@ -130,9 +111,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_kernel(const Args a)
                 for (int r = 0; r < 16; ++r) acc[i][j][p][r] = 0.f;
 
     float xa[8 * E], xb[8 * E];                // 8 k of one row / column: element e at [E e], (re, im) interleaved
-    // Whole tile inside the matrix and (where the loads are 16 bytes) 16-byte addressable (workgroup-uniform): its full K steps
-    // run in a loop of their own whose loads have no branch per lane - all loads of a step are in flight together, behind the
-    // MFMAs of the step before, and are waited for only where they are split.  Everything else takes the guarded loads.
+    // the fast loads want the whole tile inside the matrix and, where they are 16 bytes, 16-byte addressable (k_loop, gemm_sp_frame.h)
     const bool tile_fast = (!OPC || a.vecA) && a.vecB && m0 + BM <= a.m && n0 + BN <= a.n;
     // k-contiguous piece: 8 E floats from p
     auto load_k_fast = [&](const float* p, float* x) {
@@ -272,161 +251,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_kernel(const Args a)
             }
         }
     };
-    // K steps [t0, t1) with one kind of load: step t + 1 is fetched into registers while step t is multiplied from LDS
-    auto pipeline = [&](int t0, int t1, auto&& load) {
-        if (t0 >= t1) return;
-        load((long)t0 * BK);
-        store_tiles(0);
-        __syncthreads();
-        int buf = 0;
-        for (int t = t0; t + 1 < t1; ++t) {
-            load((long)(t + 1) * BK);
-            __builtin_amdgcn_sched_barrier(0);     // the loads are issued here, a whole step of MFMAs ahead of their use -
-            compute(buf);                          // left alone, the scheduler sinks them to the end of the step
-            __builtin_amdgcn_sched_barrier(0);
-            store_tiles(buf ^ 1);
-            __syncthreads();
-            buf ^= 1;
-        }
-        compute(buf);
-        __syncthreads();                           // (a following pipeline starts over in buffer 0)
-    };
-    const int T = (a.k + BK - 1) / BK;
-    if (tile_fast) {
-        const int Tf = a.k / BK;
-        pipeline(0, Tf, load_fast);
-        pipeline(Tf, T, load_slow);
-    } else {
-        pipeline(0, T, load_slow);
-    }
-
-    // epilogue, as in gemm_mfma_f32.hip.  C/D map of the 32 x 32 tile: column = lane & 31, rows 8 g + 4 (lane >> 5) + (0..3) in
-    // registers 4 g .. 4 g + 3
-    if constexpr (WIDE) {
-        const bool useC = (a.wbr != 0.0) || (a.wbi != 0.0);
-        #pragma unroll
-        for (int i = 0; i < 2; ++i)
-            #pragma unroll
-            for (int j = 0; j < WN; ++j) {
-                const long col = n0 + wn * (32 * WN) + 32 * j + lr;
-                if (col >= a.n) continue;
-                #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const long row = m0 + wm * 64 + 32 * i + 8 * g + 4 * lh;
-                    if (row >= a.m) continue;
-                    double* c = a.Cw + E * (row + col * a.ldc);
-                    const bool vec = a.vecC && row + 4 <= a.m;
-                    double o[4 * E], c0[4 * E];
-                    #pragma unroll
-                    for (int q = 0; q < 4 * E; ++q) c0[q] = 0.0;
-                    if (useC) {
-                        if (vec) {
-                            #pragma unroll
-                            for (int q = 0; q < 2 * E; ++q) {
-                                const double2 t = ((const double2*)c)[q];
-                                c0[2 * q] = t.x; c0[2 * q + 1] = t.y;
-                            }
-                        } else {
-                            #pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                if (row + e < a.m) {
-                                    #pragma unroll
-                                    for (int p = 0; p < E; ++p) c0[E * e + p] = c[E * e + p];
-                                }
-                        }
-                    }
-                    #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        if constexpr (CPLX) {
-                            const double xr = (double)acc[i][j][0][4 * g + e], xi = (double)acc[i][j][1][4 * g + e];
-                            double yr = a.war * xr - a.wai * xi, yi = a.war * xi + a.wai * xr;
-                            if (useC) {
-                                yr += a.wbr * c0[2 * e] - a.wbi * c0[2 * e + 1];
-                                yi += a.wbr * c0[2 * e + 1] + a.wbi * c0[2 * e];
-                            }
-                            o[2 * e] = yr; o[2 * e + 1] = yi;
-                        } else {
-                            double y = a.war * (double)acc[i][j][0][4 * g + e];
-                            if (useC) y += a.wbr * c0[e];
-                            o[e] = y;
-                        }
-                    }
-                    if (vec) {
-                        #pragma unroll
-                        for (int q = 0; q < 2 * E; ++q) ((double2*)c)[q] = make_double2(o[2 * q], o[2 * q + 1]);
-                    } else {
-                        #pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (row + e < a.m) {
-                                #pragma unroll
-                                for (int p = 0; p < E; ++p) c[E * e + p] = o[E * e + p];
-                            }
-                    }
-                }
-            }
-        return;
-    }
-    const bool useC = (a.br != 0.f) || (a.bi != 0.f);
-    #pragma unroll
-    for (int i = 0; i < 2; ++i)
-        #pragma unroll
-        for (int j = 0; j < WN; ++j) {
-            const long col = n0 + wn * (32 * WN) + 32 * j + lr;
-            if (col >= a.n) continue;
-            #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const long row = m0 + wm * 64 + 32 * i + 8 * g + 4 * lh;
-                if (row >= a.m) continue;
-                float* c = a.C + E * (row + col * a.ldc);
-                const bool vec = a.vecC && row + 4 <= a.m;
-                float o[4 * E], c0[4 * E];
-                #pragma unroll
-                for (int q = 0; q < 4 * E; ++q) c0[q] = 0.f;
-                if (useC) {
-                    if (vec) {
-                        #pragma unroll
-                        for (int q = 0; q < E; ++q) {
-                            const float4 t = ((const float4*)c)[q];
-                            c0[4 * q] = t.x; c0[4 * q + 1] = t.y; c0[4 * q + 2] = t.z; c0[4 * q + 3] = t.w;
-                        }
-                    } else {
-                        #pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            if (row + e < a.m) {
-                                #pragma unroll
-                                for (int p = 0; p < E; ++p) c0[E * e + p] = c[E * e + p];
-                            }
-                    }
-                }
-                #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if constexpr (CPLX) {
-                        const float xr = acc[i][j][0][4 * g + e], xi = acc[i][j][1][4 * g + e];
-                        float yr = a.ar * xr - a.ai * xi, yi = a.ar * xi + a.ai * xr;
-                        if (useC) {
-                            yr += a.br * c0[2 * e] - a.bi * c0[2 * e + 1];
-                            yi += a.br * c0[2 * e + 1] + a.bi * c0[2 * e];
-                        }
-                        o[2 * e] = yr; o[2 * e + 1] = yi;
-                    } else {
-                        float y = a.ar * acc[i][j][0][4 * g + e];
-                        if (useC) y += a.br * c0[e];
-                        o[e] = y;
-                    }
-                }
-                if (vec) {
-                    #pragma unroll
-                    for (int q = 0; q < E; ++q) ((float4*)c)[q] = make_float4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
-                } else {
-                    #pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (row + e < a.m) {
-                            #pragma unroll
-                            for (int p = 0; p < E; ++p) c[E * e + p] = o[E * e + p];
-                        }
-                }
-            }
-        }
+    k_loop<BK>(a.k, tile_fast, load_fast, load_slow, store_tiles, compute);
+#include "gemm_sp_epilogue.h"    // the epilogue, as text: uses a, at, acc (the file says why it is no function)
 }
 
 template <bool CPLX, int WN, bool OPC = false, bool WIDE = false>
@@ -437,75 +263,30 @@ int launch(hipStream_t st, const Args& a, int tag)
     return (int)hipGetLastError();
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// tile width of a real product, by the rule of gemm_mfma_f32.hip: 128 columns unless the 64-column form fills the last round of workgroups better
-int tile_cols(int m, int n, int num_cu)
-{
-    if (num_cu <= 0) num_cu = 256;
-    const long gm = ((long)m + BM - 1) / BM;
-    const long t128 = gm * (((long)n + 127) / 128), t64 = gm * (((long)n + 63) / 64);
-    // rounds in units of a 128 x 64 tile: a 128-column tile costs two
-    const long r128 = 2 * ((t128 + num_cu - 1) / num_cu), r64 = (t64 + num_cu - 1) / num_cu;
-    return r64 < r128 ? 64 : 128;
-}
-
-// the tile grid and the 16-byte flags of the fp32 operands (vecA is only used for op = C, whose A is read along k like B);
-// false: more tiles than a launch can hold
-bool plan(Args& a, bool cplx, int m, int n, int k, const float* A, long lda, const float* B, long ldb, int bn)
-{
-    a.m = m; a.n = n; a.k = k < 0 ? 0 : k;
-    a.A = A; a.lda = lda; a.B = B; a.ldb = ldb;
-    const long gm = ((long)m + BM - 1) / BM, gn = ((long)n + bn - 1) / bn;
-    if (gm * gn > 0x7fffffffL) return false;
-    a.gn = (int)gn;
-    a.total = (unsigned)(gm * gn);
-    const long ldmask = cplx ? 1 : 3;          // leading dimension in 16-byte units
-    a.vecA = (a.k > 0 && al16(A) && (lda & ldmask) == 0) ? 1 : 0;
-    a.vecB = (a.k > 0 && al16(B) && (ldb & ldmask) == 0) ? 1 : 0;
-    return true;
-}
-
 } // namespace
 
 int gemm_bf16x3w(hipStream_t st, bool cplx, char opA, int m, int n, int k, const double* alpha, const float* A, long lda,
                  const float* B, long ldb, const double* beta, double* C, long ldc, int num_cu, int tag)
 {
-    const bool opn = opA == 'N' || opA == 'n';
-    const bool opc = opA == 'C' || opA == 'c' || (!cplx && (opA == 'T' || opA == 't'));
-    if (!opn && !opc) return GEMM_F32_EOP;
-    if (m <= 0 || n <= 0) return 0;
     const int bn = cplx ? 64 : tile_cols(m, n, num_cu);
-    Args a;
-    if (!plan(a, cplx, m, n, k, A, lda, B, ldb, bn)) return (int)hipErrorInvalidValue;
-    a.ar = a.ai = a.br = a.bi = 0.f; a.C = nullptr;
-    a.war = alpha[0]; a.wai = cplx ? alpha[1] : 0.0;
-    a.wbr = beta[0]; a.wbi = cplx ? beta[1] : 0.0;
-    a.Cw = C; a.ldc = ldc;
-    a.vecC = (al16(C) && (cplx || (ldc & 1) == 0)) ? 1 : 0;       // 16 bytes: two real / one complex fp64 element
-    if (cplx) {
-        if (opc) return launch<true, 1, true, true>(st, a, tag);
-        return launch<true, 1, false, true>(st, a, tag);
-    }
-    if (opc) return bn == 64 ? launch<false, 1, true, true>(st, a, tag) : launch<false, 2, true, true>(st, a, tag);
-    return bn == 64 ? launch<false, 1, false, true>(st, a, tag) : launch<false, 2, false, true>(st, a, tag);
+    return wide(cplx, opA, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, bn, [&](const Args& a, bool opc) {
+        if (cplx) {
+            if (opc) return launch<true, 1, true, true>(st, a, tag);
+            return launch<true, 1, false, true>(st, a, tag);
+        }
+        if (opc) return bn == 64 ? launch<false, 1, true, true>(st, a, tag) : launch<false, 2, true, true>(st, a, tag);
+        return bn == 64 ? launch<false, 1, false, true>(st, a, tag) : launch<false, 2, false, true>(st, a, tag);
+    });
 }
 
 int gemm_bf16x3(hipStream_t st, bool cplx, char opA, int m, int n, int k, const float* alpha, const float* A, long lda,
                 const float* B, long ldb, const float* beta, float* C, long ldc, int num_cu, int tag)
 {
-    if (opA != 'N' && opA != 'n') return GEMM_F32_EOP;
-    if (m <= 0 || n <= 0) return 0;
     const int bn = cplx ? 64 : tile_cols(m, n, num_cu);
-    Args a;
-    if (!plan(a, cplx, m, n, k, A, lda, B, ldb, bn)) return (int)hipErrorInvalidValue;
-    a.ar = alpha[0]; a.ai = cplx ? alpha[1] : 0.f;
-    a.br = beta[0]; a.bi = cplx ? beta[1] : 0.f;
-    a.C = C; a.ldc = ldc;
-    a.war = a.wai = a.wbr = a.wbi = 0.0; a.Cw = nullptr;
-    a.vecC = (al16(C) && (ldc & (cplx ? 1 : 3)) == 0) ? 1 : 0;
-    if (cplx) return launch<true, 1>(st, a, tag);
-    return bn == 64 ? launch<false, 1>(st, a, tag) : launch<false, 2>(st, a, tag);
+    return narrow(cplx, opA, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, bn, [&](const Args& a) {
+        if (cplx) return launch<true, 1>(st, a, tag);
+        return bn == 64 ? launch<false, 1>(st, a, tag) : launch<false, 2>(st, a, tag);
+    });
 }
 
 } // namespace chase_hip

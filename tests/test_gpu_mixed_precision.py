@@ -7,10 +7,16 @@ errs by at most gamma_k |a|.|b|; alpha, beta and the final sum add a handful of 
 u = 2^-24; complex arithmetic from four real products doubles the chain: (2k + 16) u with moduli.  Derived, not tuned: an
 independent fp32 product (OpenBLAS) stays below 0.07 of it on these cases, a row of A rotated by one element exceeds it 1000-fold."""
 import ctypes as C
+import json
+import os
+import sys
 
 import numpy as np
 import pytest
 from oracle import chase_oracle as O
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import sp_gemm_hash_cases as HC  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -24
@@ -22,7 +28,10 @@ SHAPES = [(1, 1, 1, 1, 1, 1, 0),
           (130, 70, 37, 130, 37, 130, 0),                 # ragged every way
           (257, 129, 515, 257, 515, 257, 0),              # several tiles plus rests
           (1001, 160, 1001, 1001, 1001, 1001, 1),         # the filter's shape at odd N: B, C start at column 1 - unaligned base
-          (130, 70, 40, 132, 40, 132, 0)]                 # 16-byte path (aligned leading dimensions) with ragged rows and columns
+          (130, 70, 40, 132, 40, 132, 0),                 # 16-byte path (aligned leading dimensions) with ragged rows and columns
+          # 128-column tiles, ragged in m and n with a K rest: on a device with num_cu = 256 compute units 65 row panels give 260
+          # tiles of 128 x 64 against 130 of 128 x 128, two rounds either way (every shape above picks 64-column tiles there)
+          (8200, 250, 37, 8200, 37, 8200, 0)]
 SCALARS = {False: [(1.0, 0.0), (0.37, -1.25), (-2.5, 1.0)],
            True: [(1.0, 0.0), (0.37, -1.25), (0.3 - 0.7j, 1.1 + 0.4j)]}
 
@@ -96,6 +105,23 @@ def test_f32_product_within_the_fma_chain_bound(ctx, operands, shape, cplx):
     finally:
         for d in (dA, dB, dC):
             d.free()
+
+
+def test_single_precision_products_keep_their_bits(ctx):
+    """tests/golden/sp_gemm_hashes.json holds the 64-bit content hashes of 72 products - fp32 MFMA and bf16x3, real and complex,
+    narrow and wide, op N and C, both tile widths, 16-byte and guarded paths, both kernel tags, beta = 0 - as the two kernels
+    produced them before their frame moved into gemm_sp_frame.h (tests/sp_gemm_hash_cases.py wrote it on a build of that commit).
+    The inputs are device-generated from fixed seeds and the kernels have one summation order per element, so the hashes pin the
+    kernels' bits: a change of the frame must not move one."""
+    gold = json.load(open(HC.GOLDEN))
+    # on another CU count the tile-width rule picks other widths: the hashes would still match (an element's sum does not depend
+    # on the width) while the 128-column kernels went unrun
+    assert ctx.info()["num_cu"] == gold["num_cu"] == 256
+    gold = gold["rows"]
+    assert len(gold) == HC.COUNT == 72
+    rows = HC.run_cases(ctx)
+    bad = [(g, r["hash"]) for g, r in zip(gold, rows) if g != r]
+    assert not bad, bad[:4]
 
 
 @pytest.mark.parametrize("cplx", [False, True])

@@ -31,7 +31,10 @@ SHAPES = [(1, 1, 1, 0, 0, 0, 0),
           (1001, 160, 1001, 0, 0, 0, 1),              # the filter's shape at odd N: B, C start at column 1 - unaligned base
           (130, 70, 40, 2, 0, 2, 0),                  # 16-byte paths (aligned leading dimensions) with ragged rows and columns
           (70, 33, 300, 0, 0, 0, 0),                  # one ragged tile, long K: m << k as on a rank
-          (130, 7, 0, 0, 1, 0, 0)]                    # k = 0: beta C
+          (130, 7, 0, 0, 1, 0, 0),                    # k = 0: beta C
+          # 128-column tiles, ragged in m and n with a K rest: on a device with num_cu = 256 compute units 65 row panels give 260
+          # tiles of 128 x 64 against 130 of 128 x 128, two rounds either way (every shape above picks 64-column tiles there)
+          (8200, 250, 37, 0, 0, 0, 0)]
 SCALARS = {False: [(1.0, 0.0), (0.37, -1.25), (-2.5, 1.0)],                         # tests/test_gpu_mixed_precision.py
            True: [(1.0, 0.0), (0.37, -1.25), (0.3 - 0.7j, 1.1 + 0.4j)]}
 

@@ -34,7 +34,10 @@ NARROW = [(1, 1, 1, 1, 1, 1, 0),
           (257, 129, 515, 257, 515, 257, 0),              # several tiles plus rests
           (1001, 160, 1001, 1001, 1001, 1001, 1),         # the filter's shape at odd N: B, C start at column 1 - unaligned base
           (130, 70, 40, 132, 40, 132, 0),                 # 16-byte path (aligned leading dimensions) with ragged rows and columns
-          (5, 3, 11, 5, 11, 5, 0)]                        # k below one MFMA step and no multiple of 8
+          (5, 3, 11, 5, 11, 5, 0),                        # k below one MFMA step and no multiple of 8
+          # 128-column tiles (real), ragged in m and n with a K rest: on a device with num_cu = 256 compute units 65 row panels give
+          # 260 tiles of 128 x 64 against 130 of 128 x 128, two rounds either way (every shape above picks 64-column tiles there)
+          (8200, 250, 37, 8200, 37, 8200, 0)]
 # wide form (tests/test_gpu_mixed_precision_grid.py): (m, n, k, padding of lda, ldb, ldc, first column of B and C)
 WIDE = [(1, 1, 1, 0, 0, 0, 0),
         (128, 128, 64, 0, 0, 0, 0),
@@ -44,7 +47,8 @@ WIDE = [(1, 1, 1, 0, 0, 0, 0),
         (130, 70, 40, 2, 0, 2, 0),                        # 16-byte paths with ragged rows and columns
         (70, 33, 300, 0, 0, 0, 0),                        # one ragged tile, long K: m << k as on a rank
         (130, 7, 0, 0, 1, 0, 0),                          # k = 0: beta C
-        (5, 3, 11, 0, 0, 0, 0)]
+        (5, 3, 11, 0, 0, 0, 0),
+        (8200, 250, 37, 0, 0, 0, 0)]                      # 128-column tiles (real) on num_cu = 256, as in NARROW
 SCALARS = {False: [(1.0, 0.0), (0.37, -1.25), (-2.5, 1.0)],
            True: [(1.0, 0.0), (0.37, -1.25), (0.3 - 0.7j, 1.1 + 0.4j)]}
 
