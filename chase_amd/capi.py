@@ -233,6 +233,16 @@ class Context:
             f = lib.chase_hip_gemm_sd_bf16x3 if split else lib.chase_hip_gemm_sd
             check(f(self.h, op, m, n, k, float(alpha), A, lda, B, ldb, float(beta), Cm, ldc), "gemm_sd")
 
+    def set_gemm_min_rounds(self, rounds):
+        """chase_hip_ctx_set_gemm_min_rounds: > 0 while products share the chip with a collective (they are cut along K)."""
+        check(lib.chase_hip_ctx_set_gemm_min_rounds(self.h, int(rounds)), "ctx_set_gemm_min_rounds")
+
+    def gemm_sp_counters(self, reset=False):
+        """(wide_calls, split_calls, pieces) of the gemm32w products of this context (chase_hip_ctx_gemm_sp_counters)."""
+        w, s, p = C.c_ulonglong(), C.c_ulonglong(), C.c_ulonglong()
+        check(lib.chase_hip_ctx_gemm_sp_counters(self.h, C.byref(w), C.byref(s), C.byref(p), int(reset)), "ctx_gemm_sp_counters")
+        return w.value, s.value, p.value
+
     def diag_list_d2s(self, H, ldh, Hs, ldhs, rows, cols, cnt, cplx):
         """Hs[rows[i], cols[i]] (fp32) = H[rows[i], cols[i]] (fp64), i < cnt; rows, cols: device addresses of int32 lists."""
         check(lib.chase_hip_diag_list_d2s(self.h, int(cplx), H, ldh, Hs, ldhs, rows, cols, cnt), "diag_list_d2s")
@@ -495,6 +505,31 @@ def gemm_plan(cplx, op, m, n, k, lda=None, ldb=None, aligned=True, phase=0, num_
     out = (GemmLaunch * max(cnt, 1))()
     assert lib.chase_hip_gemm_plan(*args, out, cnt) == cnt
     return [out[i].as_dict() for i in range(cnt)]
+
+
+class GemmSpLaunch(C.Structure):
+    """chase_hip_gemm_sp_launch (include/chase_hip.h)"""
+    _fields_ = [(n, c_int) for n in ("bn", "gm", "gn", "sk", "kchunk", "min_piece_k")] + [("slab_bytes", c_size_t)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+_sig("chase_hip_gemm_sp_plan", c_int, c_int, c_int, c_char, c_int, c_int, c_int, c_int, c_int, P(GemmSpLaunch))
+_sig("chase_hip_gemm_sp_workspace_bytes", c_size_t, c_int, c_int, c_char, c_int, c_int, c_int, c_int, c_int)
+_sig("chase_hip_ctx_gemm_sp_counters", c_int, c_void_p, P(C.c_ulonglong), P(C.c_ulonglong), P(C.c_ulonglong), c_int)
+
+
+def gemm_sp_plan(cplx, op, m, n, k, split=False, num_cu=256, min_rounds=0):
+    """The launch chase_hip_gemm_sd / _cz (split: their bf16x3 twins) make for this product while the context's gemm_min_rounds
+    is min_rounds, as a dict (chase_hip_gemm_sp_plan; host-only): tiles, K pieces and their workspace."""
+    out = GemmSpLaunch()
+    check(lib.chase_hip_gemm_sp_plan(int(split), int(cplx), op.encode(), m, n, k, num_cu, min_rounds, C.byref(out)), "gemm_sp_plan")
+    return out.as_dict()
+
+
+def gemm_sp_workspace_bytes(cplx, op, m, n, k, split=False, num_cu=256, min_rounds=0):
+    return lib.chase_hip_gemm_sp_workspace_bytes(int(split), int(cplx), op.encode(), m, n, k, num_cu, min_rounds)
 
 
 class Solver:

@@ -7,6 +7,7 @@
 #include "../../include/chase_hip.h"
 #include "ctx.h"
 #include "kernels.h"
+#include "gemm_sp_frame.h"
 
 namespace chase_hip {
 thread_local std::string g_last_error;
@@ -317,10 +318,21 @@ static int gemm32w(chase_hip_ctx* c, bool cplx, char opA, int m, int n, int k, c
                                  : (cplx ? (opn ? "gemm_czN" : "gemm_czC") : (opn ? "gemm_sdN" : "gemm_sdC"));
         c->oplog_add(name, m, n, k, c->phase * 100);
     }
+    // gemm_min_rounds > 0: the product may be cut into K pieces (sp_frame::split_plan) - the slabs live in the context's
+    // split-K workspace, sized for the shape as chase_hip_ctx::gemm sizes it; 0: not one launch or allocation more than before
+    if (c->gemm_min_rounds > 0) {
+        const size_t need = chase_hip_gemm_sp_workspace_bytes(split, cplx, opA, m, n, k, c->num_cu, c->gemm_min_rounds);
+        if (need && (rc = c->ensure_ws((need + ((size_t)32 << 20) - 1) & ~(((size_t)32 << 20) - 1)))) return rc;
+    }
+    int pieces = 1;
     int e = (split ? gemm_bf16x3w : gemm_f32w)(c->stream, cplx, opA, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, c->num_cu,
-                                               c->phase == 1 ? 1 : 0);
+                                               c->phase == 1 ? 1 : 0, (double*)c->ws, c->ws_bytes, c->gemm_min_rounds, &pieces);
     if (e == GEMM_F32_EOP) return set_error(CHASE_HIP_EINVAL, "gemm_sd / gemm_cz: bad opA");
+    if (e == GEMM_F64_EWORKSPACE)
+        return set_error(CHASE_HIP_EINVAL, "gemm_sd / gemm_cz: split-K workspace smaller than gemm_sp_workspace_bytes for this shape");
     if (e) return hip_fail((hipError_t)e, split ? "gemm_bf16x3w launch" : "gemm_f32w launch");
+    ++c->sp_wide_calls;
+    if (pieces > 1) { ++c->sp_split_calls; c->sp_pieces += (unsigned long long)pieces; }
     return 0;
 }
 
@@ -352,6 +364,43 @@ int chase_hip_gemm_cz_bf16x3(chase_hip_ctx* c, char opA, int m, int n, int k, co
     if (!c) return set_error(CHASE_HIP_EINVAL, "ctx == NULL");
     if (!alpha || !beta) return set_error(CHASE_HIP_EINVAL, "gemm_cz: NULL alpha/beta");
     return gemm32w(c, true, opA, m, n, k, alpha, (const float*)A, lda, (const float*)B, ldb, beta, (double*)C, ldc, true);
+}
+
+/* the launch of a wide single-precision product (chase_hip_gemm_sd / _cz, bf16x3 != 0: their _bf16x3 twins) on a device with
+ * num_cu compute units while the context's gemm_min_rounds is min_rounds: host only, a pure function of its arguments */
+int chase_hip_gemm_sp_plan(int bf16x3, int cplx, char opA, int m, int n, int k, int num_cu, int min_rounds,
+                           chase_hip_gemm_sp_launch* out)
+{
+    const bool opn = (opA == 'N' || opA == 'n'), opc = (opA == 'C' || opA == 'c' || (!cplx && (opA == 'T' || opA == 't')));
+    if (!opn && !opc) return set_error(CHASE_HIP_EINVAL, "gemm_sp_plan: opA must be 'N' or 'C'");
+    if (m < 0 || n < 0 || k < 0 || !out) return set_error(CHASE_HIP_EINVAL, "gemm_sp_plan: bad argument");
+    const int kind = bf16x3 ? sp_frame::KIND_BF16X3 : sp_frame::KIND_F32;
+    const int bn = sp_frame::wide_tile_cols(kind, cplx != 0, m, n, num_cu);
+    const sp_frame::SplitPlan sp = sp_frame::split_plan(kind, cplx != 0, m, n, k, bn, num_cu, min_rounds);
+    out->bn = bn;
+    out->gm = (int)(((long)m + sp_frame::BM - 1) / sp_frame::BM);
+    out->gn = (int)(((long)n + bn - 1) / bn);
+    out->sk = sp.sk;
+    out->kchunk = sp.kchunk;
+    out->min_piece_k = sp_frame::min_piece_k(kind, cplx != 0);
+    out->slab_bytes = sp.slab_bytes;
+    return 0;
+}
+/* bytes of split-K workspace that launch uses (0: whole K) */
+size_t chase_hip_gemm_sp_workspace_bytes(int bf16x3, int cplx, char opA, int m, int n, int k, int num_cu, int min_rounds)
+{
+    chase_hip_gemm_sp_launch l;
+    return chase_hip_gemm_sp_plan(bf16x3, cplx, opA, m, n, k, num_cu, min_rounds, &l) == 0 ? l.slab_bytes : 0;
+}
+int chase_hip_ctx_gemm_sp_counters(chase_hip_ctx* c, unsigned long long* wide_calls, unsigned long long* split_calls,
+                                   unsigned long long* pieces, int reset)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "gemm_sp_counters: NULL context");
+    if (wide_calls) *wide_calls = c->sp_wide_calls;
+    if (split_calls) *split_calls = c->sp_split_calls;
+    if (pieces) *pieces = c->sp_pieces;
+    if (reset) c->sp_wide_calls = c->sp_split_calls = c->sp_pieces = 0;
+    return 0;
 }
 
 /* bytes of split-K workspace chase_hip_gemm_{d,z} uses for this shape on a device with num_cu compute units (a pure function

@@ -21,6 +21,9 @@ struct chase_hip_ctx {
     double flops_model[4] = {0, 0, 0, 0}, flops_exec[4] = {0, 0, 0, 0};
     unsigned long long gemm_calls[4] = {0, 0, 0, 0};
     int gemm_min_rounds = 0;          // > 0: products share the chip with a collective (chase_hip_ctx_set_gemm_min_rounds)
+    // wide single-precision products (chase_hip_gemm_sd / _cz and their bf16x3 twins): calls, those of them cut into K pieces
+    // under gemm_min_rounds, and the pieces of those (chase_hip_ctx_gemm_sp_counters)
+    unsigned long long sp_wide_calls = 0, sp_split_calls = 0, sp_pieces = 0;
     void* ws = nullptr;          // split-K slabs, grown on demand
     size_t ws_bytes = 0;
     enum { BUF_TINV = 0, BUF_PANEL, BUF_SCAL, BUF_LAMBDA, BUF_RR, BUF_EIG, BUF_STEDC, BUF_APPLYQ, NBUF };

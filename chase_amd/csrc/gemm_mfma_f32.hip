@@ -34,8 +34,9 @@ constexpr int KROWS = 16;          // LDS rows per tile image: 16 k (real) or 2 
 // TAG only gives the launches of the Chebyshev filter (context phase 1) a kernel symbol of their own (profiles list them apart)
 // OPC: op(A) = A^H from a k x m array.  WIDE: epilogue in fp64 on an fp64 C.
 template <bool CPLX, int WN, int TAG, bool OPC = false, bool WIDE = false>
-__global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const Args a)
+__global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const Args launch_args)
 {
+    const Args a = piece_of<CPLX, OPC, WIDE>(launch_args);     // this workgroup's K piece: the launch itself unless the host cut K
     constexpr int BN = 64 * WN;
     constexpr int LDA_T = BM, LDB_T = BN;      // LDS row strides of the two images
     constexpr int E = CPLX ? 2 : 1;            // floats per element
@@ -233,18 +234,21 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const Args a)
 template <bool CPLX, int WN, bool OPC = false, bool WIDE = false>
 int launch(hipStream_t st, const Args& a, int tag)
 {
-    if (tag == 1) hipLaunchKernelGGL((gemm_f32_kernel<CPLX, WN, 1, OPC, WIDE>), dim3(a.total), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((gemm_f32_kernel<CPLX, WN, 0, OPC, WIDE>), dim3(a.total), dim3(256), 0, st, a);
+    if (tag == 1) hipLaunchKernelGGL((gemm_f32_kernel<CPLX, WN, 1, OPC, WIDE>), dim3(a.total, a.sk), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((gemm_f32_kernel<CPLX, WN, 0, OPC, WIDE>), dim3(a.total, a.sk), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
 
 } // namespace
 
 int gemm_f32w(hipStream_t st, bool cplx, char opA, int m, int n, int k, const double* alpha, const float* A, long lda,
-              const float* B, long ldb, const double* beta, double* C, long ldc, int num_cu, int tag)
+              const float* B, long ldb, const double* beta, double* C, long ldc, int num_cu, int tag, double* ws, size_t ws_bytes,
+              int min_rounds, int* pieces)
 {
-    const int bn = tile_cols(m, n, num_cu);
-    return wide(cplx, opA, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, bn, [&](const Args& a, bool opc) {
+    const int bn = wide_tile_cols(KIND_F32, cplx, m, n, num_cu);
+    const SplitPlan sp = split_plan(KIND_F32, cplx, m, n, k, bn, num_cu, min_rounds);
+    if (pieces) *pieces = sp.sk;
+    return wide(st, cplx, opA, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, bn, sp, ws, ws_bytes, [&](const Args& a, bool opc) {
         if (cplx) {
             if (opc) return bn == 64 ? launch<true, 1, true, true>(st, a, tag) : launch<true, 2, true, true>(st, a, tag);
             return bn == 64 ? launch<true, 1, false, true>(st, a, tag) : launch<true, 2, false, true>(st, a, tag);

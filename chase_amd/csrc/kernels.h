@@ -37,15 +37,26 @@ int gemm_f32(hipStream_t st, bool cplx, char opA, int m, int n, int k, const flo
              long ldb, const float* beta, float* C, long ldc, int num_cu, int tag = 0);
 // the same product written and scaled in fp64: C64 = alpha op(A32) B32 + beta C64, op(A) = N or C (real: T as well), A for
 // op = C a k x m array.  alpha / beta point to 1 or 2 host doubles.  The product of the filter on a grid: the partial products
-// of the ranks are summed in fp64.
+// of the ranks are summed in fp64.  Whole K unless gemm_min_rounds asks for pieces; bitwise reproducible either way:
+// min_rounds > 0 (the launch shares the chip with a collective) cuts a product with fewer tiles than workgroup slots into
+// K pieces (sp_frame::split_plan, a function of shape, chip and min_rounds only), each an ordinary product
+// into an fp64 slab of its own in ws, and sp_slab_reduce sums the slabs in piece order.  ws_bytes below gemm_sp_ws_need:
+// GEMM_F64_EWORKSPACE.  pieces (optional): the K pieces of this product (1: whole K).
 int gemm_f32w(hipStream_t st, bool cplx, char opA, int m, int n, int k, const double* alpha, const float* A, long lda,
-              const float* B, long ldb, const double* beta, double* C, long ldc, int num_cu, int tag = 0);
+              const float* B, long ldb, const double* beta, double* C, long ldc, int num_cu, int tag = 0, double* ws = nullptr,
+              size_t ws_bytes = 0, int min_rounds = 0, int* pieces = nullptr);
 // the same two products on the bf16 matrix cores with every fp32 operand split into three bf16 parts in the kernel
 // (gemm_mfma_bf16x3.hip): six partial products per k in the fp32 accumulator.  Interfaces, statuses and reproducibility as above.
 int gemm_bf16x3(hipStream_t st, bool cplx, char opA, int m, int n, int k, const float* alpha, const float* A, long lda, const float* B,
                 long ldb, const float* beta, float* C, long ldc, int num_cu, int tag = 0);
 int gemm_bf16x3w(hipStream_t st, bool cplx, char opA, int m, int n, int k, const double* alpha, const float* A, long lda,
-                 const float* B, long ldb, const double* beta, double* C, long ldc, int num_cu, int tag = 0);
+                 const float* B, long ldb, const double* beta, double* C, long ldc, int num_cu, int tag = 0, double* ws = nullptr,
+                 size_t ws_bytes = 0, int min_rounds = 0, int* pieces = nullptr);
+// C = alpha (S_0 + S_1 + ... + S_{sk-1}) + beta C in fp64, the slabs summed in index order (vec_kernels.hip): slab p is the dense
+// lds x (columns) block at S + p * slab_stride (doubles; lds in elements, even), of which rows < m and columns < n are read.
+// alpha / beta point to 1 (real) or 2 (complex) host doubles; beta == 0: C is not read.
+int sp_slab_reduce(hipStream_t st, bool cplx, int m, int n, int sk, const double* S, long lds, long slab_stride, const double* alpha,
+                   const double* beta, double* C, long ldc);
 
 int mfma_f64_peak(hipStream_t st, double* out, int blocks, int iters);
 int stream_copy(hipStream_t st, void* dst, const void* src, size_t bytes);

@@ -206,6 +206,56 @@ __global__ __launch_bounds__(256) void convert_s2d_kernel(const float* __restric
         for (long i = 4 * n4 + (long)blockIdx.x * 256 + threadIdx.x; i < ms; i += (long)gridDim.x * 256) d[i] = (double)s[i];
     }
 }
+// The sum of the K pieces of a wide single-precision product (gemm_sp_frame.h): C = alpha (S_0 + S_1 + ... + S_{sk-1}) + beta C
+// in fp64, piece after piece in index order - one fixed order per element.  Slab p is the dense block at S + p * stride (lds_d
+// doubles per column, 16-byte aligned columns: always read 16 bytes wide; up to five of these loads are in flight per lane);
+// md = doubles per column of C (complex: (re, im) pairs), C 16 bytes wide where vec says base and ldc allow, by scalars
+// otherwise, and the last scalar of an odd real column on its own.  beta == 0: C is not read.  Streaming: (sk + 1) md ncols
+// doubles (sk + 2 with beta != 0).
+template <bool CPLX>
+__global__ __launch_bounds__(256) void sp_slab_reduce_kernel(const double* __restrict__ S, long lds_d, long stride, int sk, long md,
+                                                             int ncols, double ar, double ai, double br, double bi,
+                                                             double* __restrict__ C, long ldc_d, int vec)
+{
+    const bool useC = br != 0.0 || bi != 0.0;
+    for (int j = blockIdx.y; j < ncols; j += gridDim.y) {
+        const double* s = S + (long)j * lds_d;
+        double* c = C + (long)j * ldc_d;
+        const long n2 = md >> 1;
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n2; i += (long)gridDim.x * 256) {
+            double2 x = ((const double2*)s)[i];
+            for (int p0 = 1; p0 < sk; p0 += 4) {
+                double2 t[4];
+                #pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (p0 + q < sk) t[q] = ((const double2*)(s + (long)(p0 + q) * stride))[i];
+                #pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (p0 + q < sk) { x.x += t[q].x; x.y += t[q].y; }
+            }
+            double2 y;
+            if (CPLX) { y.x = ar * x.x - ai * x.y; y.y = ar * x.y + ai * x.x; }
+            else { y.x = ar * x.x; y.y = ar * x.y; }
+            if (useC) {
+                double2 c0;
+                if (vec) c0 = ((const double2*)c)[i];
+                else { c0.x = c[2 * i]; c0.y = c[2 * i + 1]; }
+                if (CPLX) { y.x += br * c0.x - bi * c0.y; y.y += br * c0.y + bi * c0.x; }
+                else { y.x += br * c0.x; y.y += br * c0.y; }
+            }
+            if (vec) ((double2*)c)[i] = y;
+            else { c[2 * i] = y.x; c[2 * i + 1] = y.y; }
+        }
+        if (!CPLX && (md & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+            const long i = md - 1;
+            double x = s[i];
+            for (int p = 1; p < sk; ++p) x += s[(long)p * stride + i];
+            double y = ar * x;
+            if (useC) y += br * c[i];
+            c[i] = y;
+        }
+    }
+}
 // Hs[i,i] = (float)H[i,i], both parts of a complex entry: the shadow of H follows the shifted diagonal
 __global__ void diag_d2s_kernel(const double* __restrict__ H, long ldh, float* __restrict__ Hs, long ldhs, int n, int ept)
 {
@@ -546,6 +596,21 @@ int convert_s2d(hipStream_t st, const float* src, long ld_src, double* dst, long
     if (ms <= 0 || ncols <= 0) return 0;
     const int vec = ((ld_src & 3) == 0) && ((ld_dst & 1) == 0) && (((uintptr_t)src & 15) == 0) && (((uintptr_t)dst & 15) == 0);
     hipLaunchKernelGGL(convert_s2d_kernel, grid2(ms, ncols), dim3(256), 0, st, src, ld_src, dst, ld_dst, ms, ncols, vec);
+    return (int)hipGetLastError();
+}
+int sp_slab_reduce(hipStream_t st, bool cplx, int m, int n, int sk, const double* S, long lds, long slab_stride, const double* alpha,
+                   const double* beta, double* C, long ldc)
+{
+    if (m <= 0 || n <= 0) return 0;
+    const long ept = cplx ? 2 : 1, md = m * ept;
+    if (sk < 1 || lds < m || ((lds * ept) & 1) || (slab_stride & 1) || ((uintptr_t)S & 15)) return (int)hipErrorInvalidValue;
+    const int vec = (((ldc * ept) & 1) == 0) && (((uintptr_t)C & 15) == 0);
+    if (cplx)
+        hipLaunchKernelGGL(sp_slab_reduce_kernel<true>, grid2(md / 2, n), dim3(256), 0, st, S, lds * ept, slab_stride, sk, md, n,
+                           alpha[0], alpha[1], beta[0], beta[1], C, ldc * ept, vec);
+    else
+        hipLaunchKernelGGL(sp_slab_reduce_kernel<false>, grid2(md / 2, n), dim3(256), 0, st, S, lds * ept, slab_stride, sk, md, n,
+                           alpha[0], 0.0, beta[0], 0.0, C, ldc * ept, vec);
     return (int)hipGetLastError();
 }
 int diag_list_d2s(hipStream_t st, const double* H, long ldh, float* Hs, long ldhs, const int* rows, const int* cols, int cnt, int ept)

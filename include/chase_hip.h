@@ -91,10 +91,14 @@ int chase_hip_gemm_c(chase_hip_ctx* ctx, char opA, int m, int n, int k, const fl
                      const void* B, long ldb, const float beta[2], void* C, long ldc);
 /* The fp32-input product with an fp64 result: C64 = alpha op(A32) B32 + beta C64, A and B real fp32 / interleaved complex fp32,
  * C, alpha and beta fp64.  opA is 'N' or 'C' (real: 'T' as well; anything else: CHASE_HIP_EINVAL); A is m x k for 'N' (lda >= m)
- * and k x m for 'C' (lda >= k).  The accumulation over the whole K runs on the f32-input matrix cores exactly as in gemm_s / _c;
- * alpha acc + beta C is formed in fp64.  This is the filter product of the grid solver: the ranks' partial products are summed
- * in fp64 by the collectives of the fp64 path.  Bitwise reproducible; beta == 0: C is not read; k == 0 gives beta C; not counted
- * by chase_hip_ctx_gemm_counters; launches in phase 1 carry a kernel symbol of their own. */
+ * and k x m for 'C' (lda >= k).  The accumulation runs on the f32-input matrix cores exactly as in gemm_s / _c; alpha acc + beta C
+ * is formed in fp64.  This is the filter product of the grid solver: the ranks' partial products are summed in fp64 by the
+ * collectives of the fp64 path.  Whole K unless gemm_min_rounds asks for pieces; bitwise reproducible either way: while
+ * chase_hip_ctx_set_gemm_min_rounds is > 0, a product with fewer output tiles than workgroup slots is cut into up
+ * to 8 K pieces (chase_hip_gemm_sp_plan), each an ordinary product into an fp64 slab of the context's workspace, and the slabs
+ * are summed in piece order in fp64 - no atomics, one fixed order per element, a function of shape and chip only.  beta == 0:
+ * C is not read; k == 0 gives beta C; not counted by chase_hip_ctx_gemm_counters (chase_hip_ctx_gemm_sp_counters counts them);
+ * launches in phase 1 carry a kernel symbol of their own. */
 int chase_hip_gemm_sd(chase_hip_ctx* ctx, char opA, int m, int n, int k, double alpha, const float* A, long lda, const float* B,
                       long ldb, double beta, double* C, long ldc);
 int chase_hip_gemm_cz(chase_hip_ctx* ctx, char opA, int m, int n, int k, const double alpha[2], const void* A, long lda,
@@ -113,6 +117,29 @@ int chase_hip_gemm_sd_bf16x3(chase_hip_ctx* ctx, char opA, int m, int n, int k, 
                              const float* B, long ldb, double beta, double* C, long ldc);
 int chase_hip_gemm_cz_bf16x3(chase_hip_ctx* ctx, char opA, int m, int n, int k, const double alpha[2], const void* A, long lda,
                              const void* B, long ldb, const double beta[2], void* C, long ldc);
+
+/* The launch chase_hip_gemm_sd / _cz (bf16x3 != 0: their _bf16x3 twins) make for a product on a device with num_cu compute units
+ * while the context's gemm_min_rounds is min_rounds, without making it (host-only: callable without a GPU; a pure function of
+ * its arguments).  gm x gn tiles of 128 x bn; sk K pieces per tile of kchunk k each (a multiple of 16; the last piece takes the
+ * rest: (sk - 1) kchunk < k <= sk kchunk); sk = 1: whole K, no workspace.  The rule: with min_rounds > 0 a launch of fewer
+ * tiles than workgroup slots (2 num_cu: less than one round) is cut; its work is counted in 128 x 64 tiles (a 128-column tile is
+ * two), sk = ceil(min_rounds slots / that count), at most 8, at most k / min_piece_k (64 K steps of the kernel: 1024 k, complex
+ * fp32 512) and at most what the workspace cap (640 MB) holds.  Returns 0 or CHASE_HIP_EINVAL. */
+typedef struct chase_hip_gemm_sp_launch {
+    int bn;                   /* tile columns: 128 or 64 */
+    int gm, gn;               /* output tiles along M and N */
+    int sk, kchunk;           /* K pieces per tile and their length */
+    int min_piece_k;          /* no split below 2 min_piece_k */
+    size_t slab_bytes;        /* workspace: sk dense fp64 blocks of gm 128 x gn bn elements (0 with sk = 1) */
+} chase_hip_gemm_sp_launch;
+int chase_hip_gemm_sp_plan(int bf16x3, int cplx, char opA, int m, int n, int k, int num_cu, int min_rounds,
+                           chase_hip_gemm_sp_launch* out);
+/* slab_bytes of that launch (context-owned, grown on demand) */
+size_t chase_hip_gemm_sp_workspace_bytes(int bf16x3, int cplx, char opA, int m, int n, int k, int num_cu, int min_rounds);
+/* the wide single-precision products of a context: calls, those of them that ran in K pieces, and the sum of their pieces.  Any
+ * output pointer may be NULL. */
+int chase_hip_ctx_gemm_sp_counters(chase_hip_ctx* ctx, unsigned long long* wide_calls, unsigned long long* split_calls,
+                                   unsigned long long* pieces, int reset);
 
 /* bytes of workspace a product of this shape uses on a device with num_cu compute units (context-owned, grown on
  * demand; min_rounds as in chase_hip_ctx_set_gemm_min_rounds): the split-K slabs and - complex products while the
@@ -174,7 +201,8 @@ int chase_hip_ctx_set_phase(chase_hip_ctx* ctx, int phase);
 /* Granularity of the following products: rounds > 0 says they share the chip with a collective on another stream (the panel
  * products of the pipelined distributed HEMM) - a product with fewer than `rounds` output tiles per workgroup slot is then cut
  * along K into that many pieces per slot, so that the CUs the collective's kernel takes displace a fraction of a tile and
- * not a whole one; 0 (default) = the automatic decomposition.  Results stay deterministic (fixed-order slab reduction). */
+ * not a whole one; 0 (default) = the automatic decomposition.  Results stay deterministic (fixed-order slab reduction).  The
+ * wide single-precision products (gemm_sd / _cz and their bf16x3 twins) are cut by a rule of their own: chase_hip_gemm_sp_plan. */
 int chase_hip_ctx_set_gemm_min_rounds(chase_hip_ctx* ctx, int rounds);
 
 /* ---- on-device input generators (global-index addressed, shard-safe) ------------------------------------------ */
