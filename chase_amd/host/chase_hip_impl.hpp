@@ -57,20 +57,22 @@ public:
 
     // H: N x N column-major (ldh), V1: N x (nev+nex) (ldv), ritzv: nev+nex reals.  h_on_device: H already lives in HBM
     // (it is then used in place, shifted and unshifted by the filter exactly like the reference does to its copy).
+    // ncols: number of columns of the vector blocks (nev+nex; the pseudo-Hermitian Impl derives with 2*(nev+nex)) and
+    // a_elems: elements of the small work matrix dA_ (0: (nev+nex)^2; that Impl's Rayleigh-Ritz needs 3 ncols^2)
     ChaseHip(chase_hip_ctx* ctx, std::size_t N, std::size_t nev, std::size_t nex, T* H, std::size_t ldh, T* V1,
-             std::size_t ldv, R* ritzv, bool h_on_device = false)
-        : ctx_(ctx), N_(N), nev_(nev), nex_(nex), nevex_(nev + nex), H_(H), ldh_(ldh), V1_(V1), ldv_(ldv),
-          ritzv_(ritzv), h_on_device_(h_on_device), config_(N, nev, nex), resid_(nev + nex, 0), perm_(nev + nex)
+             std::size_t ldv, R* ritzv, bool h_on_device = false, std::size_t ncols = 0, std::size_t a_elems = 0)
+        : ctx_(ctx), N_(N), nev_(nev), nex_(nex), nevex_(nev + nex), nc_(ncols ? ncols : nev + nex), H_(H), ldh_(ldh),
+          V1_(V1), ldv_(ldv), ritzv_(ritzv), h_on_device_(h_on_device), config_(N, nev, nex), resid_(nc_, 0), perm_(nc_)
     {
         if (!ctx) throw std::invalid_argument("ChaseHip: null context");
         if (N == 0 || nevex_ == 0 || nevex_ > N) throw std::invalid_argument("ChaseHip: need 0 < nev+nex <= N");
         if (ldh < N || ldv < N) throw std::invalid_argument("ChaseHip: leading dimension smaller than N");
-        for (std::size_t i = 0; i < nevex_; ++i) perm_[i] = (int)i;
+        reset_perm();
         if (h_on_device_) { dH_ = H; ldd_h_ = ldh; }
         else { alloc((void**)&dH_, N_ * N_ * sizeof(T)); ldd_h_ = N_; own_h_ = true; }
-        alloc((void**)&dV1_, N_ * nevex_ * sizeof(T));
-        alloc((void**)&dV2_, N_ * nevex_ * sizeof(T));
-        alloc((void**)&dA_, nevex_ * nevex_ * sizeof(T));
+        alloc((void**)&dV1_, N_ * nc_ * sizeof(T));
+        alloc((void**)&dV2_, N_ * nc_ * sizeof(T));
+        alloc((void**)&dA_, (a_elems ? a_elems : nevex_ * nevex_) * sizeof(T));
         alloc((void**)&dScal_, 4096);
         if (const char* e = std::getenv("CHASE_HIP_MIXED_PRECISION")) mixed_ = std::atoi(e) != 0;
         sp_split_ = sp_product_env() != 0;
@@ -86,7 +88,7 @@ public:
     std::size_t GetNex() override { return nex_; }
     std::size_t GetLanczosIter() override { return lanczosIter_; }
     std::size_t GetNumLanczos() override { return numLanczos_; }
-    std::size_t GetRitzvBlockSize() const override { return nevex_; }
+    std::size_t GetRitzvBlockSize() const override { return nc_; }
     R* GetRitzv() override { return ritzv_; }
     R* GetResid() override { return resid_.data(); }
     ConfigT& GetConfig() override { return config_; }
@@ -160,17 +162,18 @@ public:
         hv_valid_ = false;
         if (random && device_rng_) {
             // ChASEGPU behaviour: generate on the device (chase_gpu.hpp:520-525), no host staging of N x nevex
-            hip_ok(chase_hip_fill_normal(ctx_, CP, (int)N_, (int)nevex_, dV1_, (long)N_, 0, 0, (long)N_, 1337ull), "fill_normal");
+            hip_ok(chase_hip_fill_normal(ctx_, CP, (int)N_, (int)nc_, dV1_, (long)N_, 0, 0, (long)N_, 1337ull), "fill_normal");
         } else {
             if (random) {
                 std::mt19937 gen(1337.0);
                 std::normal_distribution<> d;
-                for (std::size_t j = 0; j < nevex_; ++j)
+                for (std::size_t j = 0; j < nc_; ++j)
                     for (std::size_t i = 0; i < N_; ++i) V1_[i + j * ldv_] = rnd(d, gen);
             }
-            hip_ok(chase_hip_upload_matrix(ctx_, CP, (int)N_, (int)nevex_, V1_, (long)ldv_, dV1_, (long)N_), "upload V");
+            hip_ok(chase_hip_upload_matrix(ctx_, CP, (int)N_, (int)nc_, V1_, (long)ldv_, dV1_, (long)N_), "upload V");
         }
-        hip_ok(chase_hip_lacpy(ctx_, CP, (int)N_, (int)nevex_, dV1_, (long)N_, dV2_, (long)N_), "lacpy");
+        init_vecs_hook(random);
+        hip_ok(chase_hip_lacpy(ctx_, CP, (int)N_, (int)nc_, dV1_, (long)N_, dV2_, (long)N_), "lacpy");
         reset_perm();
         upload_H();
     }
@@ -188,7 +191,7 @@ public:
         std::vector<T> h(N_);
         for (std::size_t c = 0; c < n_indices; ++c) {
             const std::size_t j = fixednev + col_indices[c];
-            if (j >= nevex_) throw std::invalid_argument("ReinitColumns: column out of range");
+            if (j >= nc_) throw std::invalid_argument("ReinitColumns: column out of range");
             for (auto& x : h) x = rnd(d, gen);
             hip_ok(chase_hip_upload_matrix(ctx_, CP, (int)N_, 1, h.data(), (long)N_, dV1_ + j * N_, (long)N_), "upload column");
             hip_ok(chase_hip_lacpy(ctx_, CP, (int)N_, 1, dV1_ + j * N_, (long)N_, dV2_ + j * N_, (long)N_), "lacpy");
@@ -199,7 +202,7 @@ public:
     {
         CHASE_PHASE(ctx_, "End");
         flush_swaps();
-        hip_ok(chase_hip_download_matrix(ctx_, CP, (int)N_, (int)nevex_, dV1_, (long)N_, V1_, (long)ldv_), "download V");
+        hip_ok(chase_hip_download_matrix(ctx_, CP, (int)N_, (int)nc_, dV1_, (long)N_, V1_, (long)ldv_), "download V");
     }
 
     // ---- filter --------------------------------------------------------------------------------------------------
@@ -305,21 +308,7 @@ public:
         CHASE_PHASE(ctx_, "QR");
         flush_swaps(); hv_valid_ = false;
         hip_ok(chase_hip_lacpy(ctx_, CP, (int)N_, (int)locked_, dV1_, (long)N_, dV2_, (long)N_), "lacpy");
-        int disable = config_.DoCholQR() ? 0 : 1;
-        if (const char* s = std::getenv("CHASE_DISABLE_CHOLQR")) disable = std::atoi(s);
-        R thld_hi = 1e8, thld_lo = 2e1;
-        if (const char* s = std::getenv("CHASE_CHOLQR1_THLD")) thld_lo = std::atof(s);
-        last_qr_variant_ = 0;
-        if (disable == 1 && cond != (R)1.0) {
-            householder();
-        } else {
-            const int variant = (cond > thld_hi) ? 3 : (cond < thld_lo ? 1 : 2);
-            last_qr_variant_ = variant;
-            const int info = chase_hip_cholqr(ctx_, CP, (int)N_, (int)nevex_, dV1_, (long)N_, dA_, (long)nevex_,
-                                              variant, (long)N_);
-            hip_ok(info, "cholqr");
-            if (info != 0) householder();
-        }
+        qr_block(cond);
         hip_ok(chase_hip_lacpy(ctx_, CP, (int)N_, (int)locked_, dV2_, (long)N_, dV1_, (long)N_), "lacpy");
     }
     int last_qr_variant() const override { return last_qr_variant_; }
@@ -428,7 +417,7 @@ public:
     void recompute_residuals(std::size_t ncols, const double* lambda, double* out) override
     {
         CHASE_PHASE(ctx_, "recompute_residuals");
-        if (ncols > nevex_) throw std::invalid_argument("recompute_residuals: more columns than the Impl holds");
+        if (ncols > nc_) throw std::invalid_argument("recompute_residuals: more columns than the Impl holds");
         flush_swaps();
         hv_valid_ = false;                                                   // dV2_ is scratch from here on
         chase_hip_ctx_set_phase(ctx_, 3);                                    // four real products per complex product, always
@@ -470,7 +459,9 @@ public:
         hip_ok(chase_hip_lacpy(ctx_, CP, (int)N_, (int)m, dV2_, (long)N_, dV1_, (long)N_), "lacpy");
     }
 
-private:
+protected:
+    virtual void init_vecs_hook(bool) {}            // pseudo-Hermitian Impl: damp the lower block of random start vectors
+    virtual T* swap_scratch() { return dV2_; }      // what flush_swaps permutes through: V2 is free whenever swaps are pending
     static T rnd(std::normal_distribution<>& d, std::mt19937& g)
     {
         if constexpr (is_cplx<T>::value) { const double re = d(g); const double im = d(g); return T(re, im); }
@@ -549,25 +540,45 @@ private:
     void householder()
     {
         last_qr_variant_ = 0;
-        hip_ok(chase_hip_houseqr(ctx_, CP, (int)N_, (int)nevex_, dV1_, (long)N_), "houseqr");
+        hip_ok(chase_hip_houseqr(ctx_, CP, (int)N_, (int)nc_, dV1_, (long)N_), "houseqr");
+    }
+    // the QR step of both sequential Impls on all nc_ columns of V1 (chase_cpu.hpp:590-776): CholQR1 / CholQR2 / shifted
+    // CholQR2 by the condition estimate, Householder when CholQR is switched off or its Cholesky factorisation fails
+    void qr_block(R cond)
+    {
+        int disable = config_.DoCholQR() ? 0 : 1;
+        if (const char* s = std::getenv("CHASE_DISABLE_CHOLQR")) disable = std::atoi(s);
+        R thld_hi = 1e8, thld_lo = 2e1;
+        if (const char* s = std::getenv("CHASE_CHOLQR1_THLD")) thld_lo = std::atof(s);
+        last_qr_variant_ = 0;
+        if (disable == 1 && cond != (R)1.0) {
+            householder();
+        } else {
+            const int variant = (cond > thld_hi) ? 3 : (cond < thld_lo ? 1 : 2);
+            last_qr_variant_ = variant;
+            const int info = chase_hip_cholqr(ctx_, CP, (int)N_, (int)nc_, dV1_, (long)N_, dA_, (long)nc_, variant, (long)N_);
+            hip_ok(info, "cholqr");
+            if (info != 0) householder();
+        }
     }
     void reset_perm()
     {
-        for (std::size_t i = 0; i < nevex_; ++i) perm_[i] = (int)i;
+        for (std::size_t i = 0; i < nc_; ++i) perm_[i] = (int)i;
         perm_dirty_ = false;
     }
-    // apply the deferred swaps: V1'[:, j] = V1[:, perm[j]]; V2 is free scratch whenever swaps are pending (see header)
+    // apply the deferred swaps: V1'[:, j] = V1[:, perm[j]] through swap_scratch()
     void flush_swaps()
     {
         if (!perm_dirty_) return;
         std::vector<int> src, dst;
-        for (std::size_t j = 0; j < nevex_; ++j)
+        for (std::size_t j = 0; j < nc_; ++j)
             if (perm_[j] != (int)j) { src.push_back(perm_[j]); dst.push_back((int)j); }
         if (!src.empty()) {
-            hip_ok(chase_hip_permute_cols(ctx_, CP, (int)N_, dV1_, (long)N_, dV2_, (long)N_, src.data(), dst.data(),
+            T* tmp = swap_scratch();
+            hip_ok(chase_hip_permute_cols(ctx_, CP, (int)N_, dV1_, (long)N_, tmp, (long)N_, src.data(), dst.data(),
                                           (int)src.size()), "permute_cols");
             if (hv_valid_)       // the cached H V follows its vectors
-                hip_ok(chase_hip_permute_cols(ctx_, CP, (int)N_, dHV_, (long)N_, dV2_, (long)N_, src.data(), dst.data(),
+                hip_ok(chase_hip_permute_cols(ctx_, CP, (int)N_, dHV_, (long)N_, tmp, (long)N_, src.data(), dst.data(),
                                               (int)src.size()), "permute_cols");
         }
         reset_perm();
@@ -641,7 +652,7 @@ private:
     }
 
     chase_hip_ctx* ctx_;
-    std::size_t N_, nev_, nex_, nevex_;
+    std::size_t N_, nev_, nex_, nevex_, nc_;          // nc_: columns of the vector blocks (nevex_ here, 2 nevex_ pseudo-Hermitian)
     T* H_; std::size_t ldh_;
     T* V1_; std::size_t ldv_;
     R* ritzv_;

@@ -9,6 +9,9 @@
 //   RR -> rayleighRitz_v2       linalg/internal/cpu/rayleighRitz.hpp:285-392
 //   Resd                        Impl/chase_cpu/chase_cpu.hpp:805-818
 //   Lanczos (S inner product)   linalg/internal/cpu/lanczos.hpp:302-470
+// Everything that is plumbing of the sequential Impl (getters, life cycle, filter timing, deferred Swap, ReinitColumns,
+// LanczosDos, recompute_residuals, the CholQR / Householder choice, allocation) is inherited from ChaseHip with a vector
+// block of 2*(nev+nex) columns; its Hermitian-only state (cached H V, fp32 shadows, residual re-check) is never switched on.
 // Column layout of the vector block: [locked | first half (unconverged) | second half (unconverged) | locked].
 // All O(N n) / O(N^2 n) work runs in the gfx950 kernels through the C ABI; the (2 nevex)^2 dense core of the
 // Rayleigh-Ritz step (potrf, three trsm, heevd) runs on the host like the reference CPU path.
@@ -18,141 +21,46 @@
 #include <cstring>
 #include <random>
 #include <vector>
-#include "../../include/chase_hip.h"
 #include "chase_hip_impl.hpp"
-#include "interface.hpp"
-#include "output_override.hpp"
-#include "roctx.hpp"
 
 namespace chase_amd {
 
 template <class T, class BaseT = ChaseBase<T>, class ConfigT = ChaseConfig<T>>
-class ChaseHipPseudo : public WithOutput<BaseT>, public HipImplExtras {
+class ChaseHipPseudo : public ChaseHip<T, BaseT, ConfigT> {
+    using P = ChaseHip<T, BaseT, ConfigT>;
+    using P::ctx_; using P::N_; using P::nevex_; using P::nc_; using P::locked_; using P::resid_;
+    using P::dH_; using P::ldd_h_; using P::dV1_; using P::dV2_; using P::dA_; using P::dScal_;
+    using P::lanczosIter_; using P::numLanczos_; using P::hemm_calls_;
+    using P::gemm; using P::flush_swaps; using P::qr_block;
 public:
     using R = Base<T>;
-    static constexpr int CP = is_cplx<T>::value ? 1 : 0;
+    using P::CP;
     static constexpr int E = CP ? 2 : 1;
 
     // H: N x N (ldh), V1: N x 2*(nev+nex) (ldv), ritzv: 2*(nev+nex) reals — the reference's pseudo constructor contract
     ChaseHipPseudo(chase_hip_ctx* ctx, std::size_t N, std::size_t nev, std::size_t nex, T* H, std::size_t ldh, T* V1,
                    std::size_t ldv, R* ritzv, bool h_on_device = false)
-        : ctx_(ctx), N_(N), nev_(nev), nex_(nex), nevex_(nev + nex), nc_(2 * (nev + nex)), H_(H), ldh_(ldh), V1_(V1),
-          ldv_(ldv), ritzv_(ritzv), h_on_device_(h_on_device), config_(N, nev, nex), resid_(2 * (nev + nex), 0),
-          perm_(2 * (nev + nex))
+        : P(checked(ctx, N, nev, nex, ldh, ldv), N, nev, nex, H, ldh, V1, ldv, ritzv, h_on_device, 2 * (nev + nex),
+            3 * (2 * (nev + nex)) * (2 * (nev + nex)))                    // dA_: 3 nc^2 for the projected matrices of RR
     {
-        if (!ctx) throw std::invalid_argument("ChaseHipPseudo: null context");
-        if (N == 0 || nevex_ == 0 || nc_ > N) throw std::invalid_argument("ChaseHipPseudo: need 0 < 2(nev+nex) <= N");
-        if (N % 2) throw std::invalid_argument("ChaseHipPseudo: N must be even (2 x 2 block structure)");
-        if (ldh < N || ldv < N) throw std::invalid_argument("ChaseHipPseudo: leading dimension smaller than N");
-        reset_perm();
-        if (h_on_device_) { dH_ = H; ldd_h_ = ldh; }
-        else { alloc((void**)&dH_, N_ * N_ * sizeof(T)); ldd_h_ = N_; }
-        alloc((void**)&dV1_, N_ * nc_ * sizeof(T));
-        alloc((void**)&dV2_, N_ * nc_ * sizeof(T));
-        alloc((void**)&dTmp_, N_ * nc_ * sizeof(T));
-        alloc((void**)&dA_, 3 * nc_ * nc_ * sizeof(T));
-        alloc((void**)&dScal_, 4096);
+        this->alloc((void**)&dTmp_, N_ * nc_ * sizeof(T));
+        this->mixed_ = false;                                             // the H^2 filter runs in fp64
         mixed_precision_env_ignored("the pseudo-Hermitian solver");
+        this->sp_split_ = false;
         sp_product_env_ignored("the pseudo-Hermitian solver");
     }
-    ~ChaseHipPseudo() override { for (void* p : owned_) chase_hip_free(ctx_, p); }
 
-    std::size_t GetN() const override { return N_; }
-    std::size_t GetNev() override { return nev_; }
-    std::size_t GetNex() override { return nex_; }
-    std::size_t GetLanczosIter() override { return lanczosIter_; }
-    std::size_t GetNumLanczos() override { return numLanczos_; }
-    std::size_t GetRitzvBlockSize() const override { return nc_; }
-    R* GetRitzv() override { return ritzv_; }
-    R* GetResid() override { return resid_.data(); }
-    ConfigT& GetConfig() override { return config_; }
-    int get_nprocs() override { return 1; }
-    int get_rank() override { return 0; }
+    bool set_mixed_precision(bool on) override { return !on; }
+    bool set_sp_product(int v) override { return v == 0; }
     bool isSym() override { return false; }
     bool isPseudoHerm() override { return true; }
     bool checkSymmetryEasy() override { return false; }
     bool checkPseudoHermicityEasy() override { return true; }
     void symOrHermMatrix(char) override {}
-    void Sort(R*, R*, R*) override {}
     void Shift(T, bool = false) override {}                   // the H^2 filter carries the shift in gamma
     void HEMM(std::size_t, T, T, std::size_t, std::size_t = 0) override
     {
         throw std::logic_error("ChaseHipPseudo: the pseudo-Hermitian filter uses HEMM_H2");
-    }
-    void set_early_locked_residuals(std::vector<R> r) override { early_ = std::move(r); }
-
-    std::size_t locked() const override { return locked_; }
-    int last_qr_variant() const override { return last_qr_variant_; }
-    double filter_ms() const override { return filter_ms_; }
-    std::size_t hemm_calls() const override { return hemm_calls_; }
-    void set_device_rng(bool f) override { device_rng_ = f; }
-    void reset_counters() override { filter_ms_ = 0; hemm_calls_ = 0; }
-    void* device_V1() override { flush_swaps(); return dV1_; }
-    std::size_t local_rows() const override { return N_; }
-
-    void Start() override { locked_ = 0; }
-
-    void initVecs(bool random) override
-    {
-        CHASE_PHASE(ctx_, "initVecs");
-        if (random && device_rng_) {
-            hip_ok(chase_hip_fill_normal(ctx_, CP, (int)N_, (int)nc_, dV1_, (long)N_, 0, 0, (long)N_, 1337ull), "fill_normal");
-        } else {
-            if (random) {
-                std::mt19937 gen(1337.0);
-                std::normal_distribution<> d;
-                for (std::size_t j = 0; j < nc_; ++j)
-                    for (std::size_t i = 0; i < N_; ++i) V1_[i + j * ldv_] = rnd(d, gen);
-            }
-            hip_ok(chase_hip_upload_matrix(ctx_, CP, (int)N_, (int)nc_, V1_, (long)ldv_, dV1_, (long)N_), "upload V");
-        }
-        if (random)   // chase_cpu.hpp:310-321: damp the lower block of the start vectors
-            hip_ok(chase_hip_scale_rows(ctx_, CP, (int)N_, (int)nc_, dV1_, (long)N_, (int)(N_ / 2), 0.001), "scale_rows");
-        hip_ok(chase_hip_lacpy(ctx_, CP, (int)N_, (int)nc_, dV1_, (long)N_, dV2_, (long)N_), "lacpy");
-        reset_perm();
-        if (!h_on_device_)
-            hip_ok(chase_hip_upload_matrix(ctx_, CP, (int)N_, (int)N_, H_, (long)ldh_, dH_, (long)ldd_h_), "upload H");
-    }
-    // chase_cpu.hpp:329-349: re-randomise the given columns (offset by fixednev) of V1 from mt19937(4242) and mirror to V2
-    void ReinitColumns(std::size_t fixednev, std::size_t const* col_indices, std::size_t n_indices) override
-    {
-        CHASE_PHASE(ctx_, "ReinitColumns");
-        if (n_indices == 0) return;
-        flush_swaps();
-        
-        std::mt19937 gen(4242);
-        std::normal_distribution<> d;
-        std::vector<T> h(N_);
-        for (std::size_t c = 0; c < n_indices; ++c) {
-            const std::size_t j = fixednev + col_indices[c];
-            if (j >= nc_) throw std::invalid_argument("ReinitColumns: column out of range");
-            for (auto& x : h) x = rnd(d, gen);
-            hip_ok(chase_hip_upload_matrix(ctx_, CP, (int)N_, 1, h.data(), (long)N_, dV1_ + j * N_, (long)N_), "upload column");
-            hip_ok(chase_hip_lacpy(ctx_, CP, (int)N_, 1, dV1_ + j * N_, (long)N_, dV2_ + j * N_, (long)N_), "lacpy");
-        }
-    }
-
-    void End() override
-    {
-        CHASE_PHASE(ctx_, "End");
-        flush_swaps();
-        hip_ok(chase_hip_download_matrix(ctx_, CP, (int)N_, (int)nc_, dV1_, (long)N_, V1_, (long)ldv_), "download V");
-    }
-
-    void FilterPhaseStart() override
-    {
-        roctx_push("chase:Filter");
-        flush_swaps();
-        chase_hip_ctx_set_phase(ctx_, 1);
-        hip_ok(chase_hip_timer_start(ctx_), "timer");
-    }
-    void FilterPhaseEnd() override
-    {
-        float ms = 0;
-        hip_ok(chase_hip_timer_stop(ctx_, &ms), "timer");
-        chase_hip_ctx_set_phase(ctx_, 0);
-        filter_ms_ += ms;
-        roctx_pop(ctx_);
     }
 
     void HEMM_H2(std::size_t block, T alpha, T beta, T gamma, std::size_t offset_left, std::size_t offset_right = 0) override
@@ -201,23 +109,7 @@ public:
         std::swap(dV1_, dV2_);
         // S-orthogonalise against the locked vectors: flip the lower half of the 2L locked columns
         hip_ok(chase_hip_scale_rows(ctx_, CP, n, (int)(2 * L), dV1_, (long)N_, (int)(N_ / 2), -1.0), "flip");
-        int disable = config_.DoCholQR() ? 0 : 1;
-        if (const char* s = std::getenv("CHASE_DISABLE_CHOLQR")) disable = std::atoi(s);
-        R thld_hi = 1e8, thld_lo = 2e1;
-        if (const char* s = std::getenv("CHASE_CHOLQR1_THLD")) thld_lo = std::atof(s);
-        last_qr_variant_ = 0;
-        if (disable == 1 && cond != (R)1.0) {
-            hip_ok(chase_hip_houseqr(ctx_, CP, n, (int)nc_, dV1_, (long)N_), "houseqr");
-        } else {
-            const int variant = (cond > thld_hi) ? 3 : (cond < thld_lo ? 1 : 2);
-            last_qr_variant_ = variant;
-            const int info = chase_hip_cholqr(ctx_, CP, n, (int)nc_, dV1_, (long)N_, dA_, (long)nc_, variant, (long)N_);
-            hip_ok(info, "cholqr");
-            if (info != 0) {
-                last_qr_variant_ = 0;
-                hip_ok(chase_hip_houseqr(ctx_, CP, n, (int)nc_, dV1_, (long)N_), "houseqr");
-            }
-        }
+        qr_block(cond);
         lacpy(nc_ - 2 * L, dV1_ + 2 * L * N_, dV2_ + L * N_);            // active block back to the middle of V2
         std::swap(dV1_, dV2_);
         lacpy(L, dV1_, dV2_);
@@ -262,25 +154,6 @@ public:
         if (resd != resid_.data() + locked_) std::memcpy(resid_.data() + locked_, resd, sub * sizeof(R));
     }
 
-    void recompute_residuals(std::size_t ncols, const double* lambda, double* out) override
-    {
-        CHASE_PHASE(ctx_, "recompute_residuals");
-        if (ncols > 2 * nevex_) throw std::invalid_argument("recompute_residuals: more columns than the Impl holds");
-        flush_swaps();
-        chase_hip_ctx_set_phase(ctx_, 3);
-        gemm('N', N_, ncols, N_, T(1), dH_, ldd_h_, dV1_, N_, T(0), dV2_, N_);
-        chase_hip_ctx_set_phase(ctx_, 0);
-        hip_ok(chase_hip_resid_norms(ctx_, CP, (int)N_, (int)ncols, dV2_, (long)N_, dV1_, (long)N_, lambda, out, 0), "resid");
-    }
-
-    void Swap(std::size_t i, std::size_t j) override
-    {
-        if (i == j) return;
-        std::swap(perm_[i], perm_[j]);
-        perm_dirty_ = true;
-    }
-    void Lock(std::size_t k) override { locked_ += k; }
-
     void Lanczos(std::size_t m, R* upperb) override
     {
         CHASE_PHASE(ctx_, "Lanczos");
@@ -296,26 +169,26 @@ public:
         lanczos_core(M, numvec, true, ritzv, Tau, ritzV);
         if (upperb) *upperb = ritzv[M - 1];                   // cpu/lanczos.hpp:515
     }
-    void LanczosDos(std::size_t idx, std::size_t m, T* ritzVc) override
+
+protected:
+    // chase_cpu.hpp:310-321: damp the lower block of random start vectors
+    void init_vecs_hook(bool random) override
     {
-        CHASE_PHASE(ctx_, "LanczosDos");
-        flush_swaps();
-        hip_ok(chase_hip_upload_matrix(ctx_, CP, (int)m, (int)idx, ritzVc, (long)m, dA_, (long)m), "upload ritzV");
-        gemm('N', N_, idx, m, T(1), dV1_, N_, dA_, m, T(0), dV2_, N_);
-        hip_ok(chase_hip_lacpy(ctx_, CP, (int)N_, (int)m, dV2_, (long)N_, dV1_, (long)N_), "lacpy");
+        if (random)
+            hip_ok(chase_hip_scale_rows(ctx_, CP, (int)N_, (int)nc_, dV1_, (long)N_, (int)(N_ / 2), 0.001), "scale_rows");
     }
+    T* swap_scratch() override { return dTmp_; }
 
 private:
-    static T rnd(std::normal_distribution<>& d, std::mt19937& g)
+    // the constructor's argument checks, run before the base class allocates anything
+    static chase_hip_ctx* checked(chase_hip_ctx* ctx, std::size_t N, std::size_t nev, std::size_t nex, std::size_t ldh,
+                                  std::size_t ldv)
     {
-        if constexpr (is_cplx<T>::value) { const double re = d(g); const double im = d(g); return T(re, im); }
-        else return T(d(g));
-    }
-    void alloc(void** p, std::size_t bytes)
-    {
-        int rc = chase_hip_malloc(ctx_, p, bytes);
-        if (rc) throw HipStatusError(rc, "chase_hip_malloc");
-        owned_.push_back(*p);
+        if (!ctx) throw std::invalid_argument("ChaseHipPseudo: null context");
+        if (N == 0 || nev + nex == 0 || 2 * (nev + nex) > N) throw std::invalid_argument("ChaseHipPseudo: need 0 < 2(nev+nex) <= N");
+        if (N % 2) throw std::invalid_argument("ChaseHipPseudo: N must be even (2 x 2 block structure)");
+        if (ldh < N || ldv < N) throw std::invalid_argument("ChaseHipPseudo: leading dimension smaller than N");
+        return ctx;
     }
     void lacpy(std::size_t ncols, const T* src, T* dst)
     {
@@ -325,30 +198,6 @@ private:
     {
         double h[2] = {std::real(v), CP ? std::imag(v) : 0.0};
         hip_ok(chase_hip_memcpy_h2d(ctx_, dScal_, h, sizeof h), "h2d");
-    }
-    void gemm(char op, std::size_t m, std::size_t n, std::size_t k, T alpha, const T* A, std::size_t lda, const T* B,
-              std::size_t ldb, T beta, T* C, std::size_t ldc)
-    {
-        int rc;
-        if constexpr (is_cplx<T>::value) {
-            const double a[2] = {alpha.real(), alpha.imag()}, b[2] = {beta.real(), beta.imag()};
-            rc = chase_hip_gemm_z(ctx_, op, (int)m, (int)n, (int)k, a, A, (long)lda, B, (long)ldb, b, C, (long)ldc);
-        } else {
-            rc = chase_hip_gemm_d(ctx_, op, (int)m, (int)n, (int)k, alpha, A, (long)lda, B, (long)ldb, beta, C, (long)ldc);
-        }
-        hip_ok(rc, "gemm");
-    }
-    void reset_perm() { for (std::size_t i = 0; i < nc_; ++i) perm_[i] = (int)i; perm_dirty_ = false; }
-    void flush_swaps()
-    {
-        if (!perm_dirty_) return;
-        std::vector<int> src, dst;
-        for (std::size_t j = 0; j < nc_; ++j)
-            if (perm_[j] != (int)j) { src.push_back(perm_[j]); dst.push_back((int)j); }
-        if (!src.empty())
-            hip_ok(chase_hip_permute_cols(ctx_, CP, (int)N_, dV1_, (long)N_, dTmp_, (long)N_, src.data(), dst.data(),
-                                          (int)src.size()), "permute_cols");
-        reset_perm();
     }
 
     // S-inner-product Lanczos (cpu/lanczos.hpp:302-470).  The per-step scalars go through the host: M <= 50 steps of
@@ -435,24 +284,7 @@ private:
         }
     }
 
-    chase_hip_ctx* ctx_;
-    std::size_t N_, nev_, nex_, nevex_, nc_;
-    T* H_; std::size_t ldh_;
-    T* V1_; std::size_t ldv_;
-    R* ritzv_;
-    bool h_on_device_;
-    ConfigT config_;
-    std::vector<R> resid_, early_;
-    std::vector<int> perm_;
-    bool perm_dirty_ = false, device_rng_ = false;
-    std::size_t locked_ = 0, lanczosIter_ = 0, numLanczos_ = 0;
-    T *dH_ = nullptr, *dV1_ = nullptr, *dV2_ = nullptr, *dTmp_ = nullptr, *dA_ = nullptr;
-    void* dScal_ = nullptr;
-    std::size_t ldd_h_ = 0;
-    std::vector<void*> owned_;
-    double filter_ms_ = 0;
-    std::size_t hemm_calls_ = 0;
-    int last_qr_variant_ = 0;
+    T* dTmp_ = nullptr;                   // N x nc scratch: H V1 of the H^2 filter, deferred swaps, Lanczos scaling
 };
 
 } // namespace chase_amd

@@ -270,3 +270,76 @@ def test_pseudo_rayleigh_ritz_dense_core(ctx, cplx, n):
     rc = lib.chase_hip_pseudo_rr_small(ctx.h, int(cplx), n, dA.ptr, dM.ptr, ritz.ctypes.data)
     assert 0 < rc <= n
     dA.free(); dM.free()
+
+
+# ---- the plumbing ChaseHipPseudo inherits from ChaseHip, on its block of 2 (nev + nex) columns -----------------------------
+
+def _block_solver(ctx):
+    """N = 64 complex, nev = nex = 4: 16 distinguishable columns (first half 0-7) uploaded with initVecs(False)"""
+    from chase_amd.capi import PseudoSolver
+    N = 64
+    H = np.asfortranarray(ctx.gen_bse(N, True, dmin=1.0, dmax=11.0, offdiag=1e-3, seed=7).download())
+    s = PseudoSolver(ctx, H, 4, 4)
+    assert s.ncol == 16
+    s.V[:] = (np.arange(1, 17) * (1 + 0.5j))[None, :] + np.arange(N)[:, None] * 1e-3
+    V0 = s.V.copy()
+    s.Start()
+    s.initVecs(False)
+    return s, V0
+
+
+def test_pseudo_deferred_swaps_cross_both_halves(ctx):
+    """A chain of deferred swaps that crosses the halves and reuses an index: a permutation sized by nev + nex instead of
+    2 (nev + nex) shows here."""
+    s, V0 = _block_solver(ctx)
+    want = V0.copy()
+    for (i, j) in [(1, 13), (2, 9), (13, 3), (0, 0)]:
+        s.Swap(i, j)
+        want[:, [i, j]] = want[:, [j, i]]
+    s.End()
+    assert np.array_equal(s.V, want)
+    s.close()
+
+
+def test_pseudo_reinit_columns_second_half_and_bound(ctx):
+    from chase_amd.capi import ChaseHipError
+    s, V0 = _block_solver(ctx)
+    s.ReinitColumns(8, [5])                                    # column 13, in the second half
+    s.End()
+    changed = [j for j in range(16) if not np.array_equal(s.V[:, j], V0[:, j])]
+    assert changed == [13]
+    with pytest.raises(ChaseHipError) as e:
+        s.ReinitColumns(8, [8])                                # column 16: one past the block
+    assert e.value.code == -1001 and "ReinitColumns: column out of range" in str(e.value)
+    s.close()
+
+
+@pytest.mark.parametrize("pseudo,N,n,text", [
+    (True, 9, 1, "solver_create_pseudo: ChaseHipPseudo: N must be even (2 x 2 block structure)"),
+    (True, 8, 3, "solver_create_pseudo: ChaseHipPseudo: need 0 < 2(nev+nex) <= N"),
+    (False, 8, 5, "solver_create: ChaseHip: need 0 < nev+nex <= N")])
+def test_sequential_constructor_texts(ctx, pseudo, N, n, text):
+    """The argument checks of both sequential Impls keep their own texts: the base class's do not pre-empt the derived one's."""
+    from chase_amd.capi import ChaseHipError, PseudoSolver, Solver
+    H = np.asfortranarray(np.eye(N, dtype=np.complex128))
+    with pytest.raises(ChaseHipError) as e:
+        (PseudoSolver if pseudo else Solver)(ctx, H, n, n)
+    assert e.value.code == -1001 and str(e.value).endswith(": " + text)
+
+
+def test_pseudo_inherited_hermitian_state_is_inert(ctx, monkeypatch):
+    """Mixed precision, the cached H V and the residual re-check of ChaseHip stay off in a Solve_pseudo, whatever the
+    environment asks for."""
+    from chase_amd.capi import PseudoSolver
+    monkeypatch.setenv("CHASE_HIP_MIXED_PRECISION", "1")
+    monkeypatch.setenv("CHASE_HIP_SP_PRODUCT", "bf16x3")
+    H = np.asfortranarray(ctx.gen_bse(64, True, dmin=1.0, dmax=11.0, offdiag=1e-3, seed=7).download())
+    s = PseudoSolver(ctx, H, 4, 4)
+    s.set(tol=1e-10, numlanczos=10, lanczositer=50)
+    s.solve()
+    for key in ("mixed_precision", "sp_product", "hemm_sp_calls", "hemm_sp_vecs", "sp_filters", "hemm_reused_vecs",
+                "resd_rechecked"):
+        assert s.get(key) == 0, key
+    calls = s.get("hemm_calls")
+    assert calls > 0 and calls % 2 == 0
+    s.close()
