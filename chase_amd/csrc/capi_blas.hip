@@ -492,8 +492,9 @@ int chase_hip_abs_trace(chase_hip_ctx* c, int cplx, int n, const void* A, long l
     return 0;
 }
 
-/* In-place upper Cholesky A = R^H R of the device matrix A (n x n); strictly-lower part untouched.
- * Returns 0 or the LAPACK info (index of the first non-positive pivot, 1-based). */
+/* In-place upper Cholesky A = R^H R of the device matrix A (n x n): R in the upper triangle.  The strictly lower triangle is
+ * never read; its contents on return are unspecified (for n > 64 the trailing updates are full products and overwrite it).
+ * Rows beyond n (lda > n) are untouched.  Returns 0 or the LAPACK info (index of the first non-positive pivot, 1-based). */
 int chase_hip_potrf_upper(chase_hip_ctx* c, int cplx, int n, void* A_, long lda)
 {
     if (!c) return set_error(CHASE_HIP_EINVAL, "potrf: NULL ctx");
@@ -671,10 +672,11 @@ int chase_hip_heevd(chase_hip_ctx* c, int cplx, int n, void* A, long lda, double
     if (n < 0 || lda < n) return set_error(CHASE_HIP_EINVAL, "heevd: bad shape");
     if (n == 0) return 0;
     {   // large projected problems: tridiagonalise and back-transform on the GPU, only the O(n^2) tridiagonal solve on
-        // the host (hetrd.hip).  CHASE_HIP_HEEVD_GPU_MIN overrides the switch-over size (0 = always host).
+        // the host (hetrd.hip).  CHASE_HIP_HEEVD_GPU_MIN overrides the switch-over size (0 = always host).  The device path
+        // needs a reflector (n >= 3): smaller sizes stay on the host whatever the switch says.
         static int thr = -1;
         if (thr < 0) { const char* e = getenv("CHASE_HIP_HEEVD_GPU_MIN"); thr = e ? atoi(e) : 384; }
-        if (thr > 0 && n >= thr) {
+        if (thr > 0 && n >= thr && n >= 3) {
             // the divide & conquer stage's launches depend on the data (deflation): the operator log lists heevd only
             ++c->oplog_mute;
             const int rc = chase_hip_heevd_gpu(c, cplx, n, A, lda, w_host);

@@ -320,7 +320,8 @@ int chase_hip_herk(chase_hip_ctx* ctx, int cplx, int n, int k, const void* V, lo
 int chase_hip_herkx(chase_hip_ctx* ctx, int cplx, int n, int k, const void* A, long lda, const void* B, long ldb, void* C,
                     long ldc, int mirror);
 int chase_hip_abs_trace(chase_hip_ctx* ctx, int cplx, int n, const void* A, long lda, double* out_host);
-/* returns 0 or LAPACK info > 0 (first non-positive pivot) */
+/* in-place upper Cholesky A = R^H R; returns 0 or LAPACK info > 0 (first non-positive or NaN pivot).  The strictly lower
+ * triangle is never read and its contents on return are unspecified; rows beyond n (lda > n) are untouched */
 int chase_hip_potrf_upper(chase_hip_ctx* ctx, int cplx, int n, void* A, long lda);
 int chase_hip_trsm_right_upper(chase_hip_ctx* ctx, int cplx, int m, int n, const void* R, long ldr, void* V, long ldv);
 /* variant 1 = cholQR1, 2 = cholQR2, 3 = shiftedcholQR2 (linalg/internal/cpu/cholqr1.hpp:41-189); returns info */
@@ -332,7 +333,8 @@ int chase_hip_houseqr(chase_hip_ctx* ctx, int cplx, int m, int n, void* V, long 
 /* ---- Rayleigh-Ritz: host HEEVD of a device matrix ('V','L'), eigenvectors back on the device -------------------- */
 int chase_hip_heevd(chase_hip_ctx* ctx, int cplx, int n, void* A, long lda, double* w_host);
 /* same contract; Householder tridiagonalisation + back-transformation on the GPU, tridiagonal stemr on the host
- * (chase_hip_heevd switches to it for n >= 384; env CHASE_HIP_HEEVD_GPU_MIN) */
+ * (chase_hip_heevd switches to it for n >= 384; env CHASE_HIP_HEEVD_GPU_MIN - sizes below 3, which this entry point refuses,
+ * always stay on the host there) */
 int chase_hip_heevd_gpu(chase_hip_ctx* ctx, int cplx, int n, void* A, long lda, double* w_host);
 /* pseudo-Hermitian (BSE) Rayleigh-Ritz: small dense part of cpu::rayleighRitz_v2 (cpu/rayleighRitz.hpp:316-383) on the host */
 int chase_hip_pseudo_rr_small(chase_hip_ctx* ctx, int cplx, int n, void* A_dev, void* M_dev, double* ritzv_host);

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 from conftest import read_ref_matrix
 from oracle import chase_oracle as O
+from dense_chain_refs import tridiag_cases as _tridiag_cases
 
 pytestmark = pytest.mark.gpu
 EPS = np.finfo(np.float64).eps
@@ -672,26 +673,6 @@ def test_filter_gemm_of_arbitrary_size_uses_3m_for_the_bulk(ctx, op, m, k, n):
     assert m1 - m0 == 2.0 * 4 * m * n * k and 0.75 < ratio < 0.80, ratio
     for d in (dA, dB, dC):
         d.free()
-
-
-def _tridiag_cases(n, rng):
-    m = (n - 1) // 2
-    dg = np.concatenate([np.abs(np.arange(21) - 10.0)] * (n // 21))
-    eg = np.ones(len(dg) - 1); eg[20::21] = 1e-8
-    ez = rng.standard_normal(n - 1); ez[::7] = 0.0
-    k = np.arange(1, n)
-    return {
-        "random": (rng.standard_normal(n), rng.standard_normal(n - 1)),
-        "toeplitz_1_2_1": (2.0 * np.ones(n), np.ones(n - 1)),
-        "wilkinson": (np.abs(np.arange(n) - m).astype(float), np.ones(n - 1)),
-        "glued_wilkinson": (dg, eg),
-        "clustered": (np.ones(n), 1e-9 * rng.standard_normal(n - 1)),
-        "graded": (10.0 ** (-np.arange(n) * 12.0 / n), 10.0 ** (-np.arange(1, n) * 12.0 / n)),
-        "zero_couplings": (rng.standard_normal(n), ez),
-        "clement": (np.zeros(n), np.sqrt(k * (n - k)) * 1e3),
-        "zero_matrix": (np.zeros(n), np.zeros(n - 1)),
-        "negative_couplings": (rng.standard_normal(n), -np.abs(rng.standard_normal(n - 1))),
-    }
 
 
 @pytest.mark.parametrize("n", [100, 129, 300, 1000, 2049])

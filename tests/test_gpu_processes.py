@@ -4,7 +4,10 @@ never hide the in-process suite again.  Never more than 4 worker processes + thi
   communication stream and per-panel events);
 * REAL RCCL collectives between 2 and 4 rank processes that share the GPU (one NCCL_HOSTID per rank -> RCCL's socket transport);
 * one 4-process host-transport run (the torch.distributed/gloo fabric bench.py's launcher and dist_bench use);
-* the reference's MPI_Comm* entry points (libchase_hip_mpi.so) on one MPI rank, and the plain-C MPI example."""
+* the reference's MPI_Comm* entry points (libchase_hip_mpi.so) on one MPI rank, and the plain-C MPI example;
+* the dense chain's CHASE_HIP_* switches, which a process reads once: four children of tests/dense_chain_worker.py, one per
+  switch set and one at a time, cover every non-default route of trsm, herkx, the back-transformation, the tridiagonalisation,
+  the tridiagonal solvers, heevd's switch-over and the pseudo-Hermitian dense core."""
 import os
 import subprocess
 import sys
@@ -201,3 +204,56 @@ def test_c_mpi_application_example(tmp_path):
     p = subprocess.run([exe, "600"], capture_output=True, text=True, timeout=600,
                        env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert p.returncode == 0 and "-> OK" in p.stdout, (p.stdout[-2000:], p.stderr[-2000:])
+
+
+# ---- the dense chain behind its switches (tests/dense_chain_worker.py) ------------------------------------------------------------
+_DEAD_CHILD = []
+
+
+def run_dense_chain(switches, cases, timeout):
+    """One child per switch set, one at a time.  A child that was killed by a signal, aborted (134), faulted (139) or ran into its
+    timeout may have left the GPU in any state: the remaining switch tests of this run then fail at once without starting
+    another GPU process."""
+    assert not _DEAD_CHILD, "an earlier child died: %s" % (_DEAD_CHILD,)
+    cmd = [sys.executable, os.path.join(ROOT, "tests", "dense_chain_worker.py"), *cases]
+    try:
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=dict(os.environ, **switches))
+    except subprocess.TimeoutExpired as e:
+        _DEAD_CHILD.append((switches, "timeout after %d s" % timeout))
+        out = e.stdout.decode(errors="replace") if isinstance(e.stdout, bytes) else (e.stdout or "")
+        raise AssertionError(("timeout", timeout, out[-2000:]))
+    if p.returncode < 0 or p.returncode in (134, 139):
+        _DEAD_CHILD.append((switches, p.returncode))
+    assert p.returncode == 0 and "DENSE_CHAIN_OK" in p.stdout, (p.returncode, p.stdout[-3000:], p.stderr[-2000:])
+
+
+# timeouts: each child's first run on an MI355X took the seconds written next to it, process start-up and the host-side long
+# double references included (the GPU part is under a second per case); 120 s leaves room for a loaded host and still ends a
+# hung child long before the suite's own limit
+def test_dense_chain_wide_blocks():
+    """blocks of 128 in trsm (the rank-64 update inside a block) and herkx (a five-column trapezoid at n = 515), back-transformation
+    panels of 64 reflectors"""
+    run_dense_chain({"CHASE_HIP_TRSM_BLOCK": "128", "CHASE_HIP_HERK_BLOCK": "128", "CHASE_HIP_APPLYQ_BLOCK": "64"},
+                    ["blocks_trsm", "blocks_herkx", "blocks_cholqr", "blocks_heevd_gpu"], timeout=120)          # measured: 5.0 s
+
+
+def test_dense_chain_first_generation_routes():
+    """unblocked tridiagonalisation, host stemr, one-GEMM herkx at every size, host potrf / trsm around the device eigensolver in
+    the pseudo-Hermitian core"""
+    run_dense_chain({"CHASE_HIP_TRD_UNBLOCKED": "1", "CHASE_HIP_TRIDIAG_MRRR": "1", "CHASE_HIP_HERK_BLOCK": "0",
+                     "CHASE_HIP_PSEUDO_RR_DEVICE": "0"},
+                    ["firstgen_heevd_gpu", "firstgen_herkx", "firstgen_pseudo_rr"], timeout=120)          # measured: 5.3 s
+
+
+def test_dense_chain_device_paths_from_three_rows():
+    """heevd on the device from 3 rows on (1 and 2 rows stay on the host and succeed), device divide & conquer below 512 rows, the
+    pseudo-Hermitian device core at 96 rows"""
+    run_dense_chain({"CHASE_HIP_HEEVD_GPU_MIN": "1", "CHASE_HIP_STEDC_GPU_MIN": "1"},
+                    ["device3_heevd", "device3_heevd_gpu", "device3_pseudo_rr"], timeout=120)          # measured: 3.5 s
+
+
+def test_dense_chain_all_host_paths():
+    """host LAPACK at sizes that go to the device by default: heevd at 700 rows, dstedc under the device tridiagonalisation at 600,
+    the pseudo-Hermitian core at 400"""
+    run_dense_chain({"CHASE_HIP_HEEVD_GPU_MIN": "0", "CHASE_HIP_STEDC_GPU_MIN": "0"},
+                    ["allhost_heevd", "allhost_heevd_gpu", "allhost_pseudo_rr"], timeout=120)          # measured: 3.4 s
