@@ -77,6 +77,13 @@ _sig("chase_hip_gemm_cz", c_int, c_void_p, c_char, c_int, c_int, c_int, P(c_doub
      c_long, P(c_double), c_void_p, c_long)
 for _n in ("s", "c", "sd", "cz"):          # the split-operand (bf16x3) forms have the signatures of the fp32 MFMA ones
     _sig("chase_hip_gemm_%s_bf16x3" % _n, c_int, *getattr(lib, "chase_hip_gemm_" + _n).argtypes)
+_sig("chase_hip_bf16x3_pack_bytes", c_int, c_int, c_int, c_int, P(c_size_t))
+_sig("chase_hip_bf16x3_pack", c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p)
+_sig("chase_hip_bf16x3_pack_diag", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p)
+_sig("chase_hip_gemm_s_bf16x3p", c_int, c_void_p, c_int, c_int, c_int, C.c_float, c_void_p, c_void_p, c_long, C.c_float, c_void_p,
+     c_long)
+_sig("chase_hip_gemm_c_bf16x3p", c_int, c_void_p, c_int, c_int, c_int, P(C.c_float), c_void_p, c_void_p, c_long, P(C.c_float),
+     c_void_p, c_long)
 _sig("chase_hip_diag_list_d2s", c_int, c_void_p, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p, c_int)
 _sig("chase_hip_convert_d2s", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
 _sig("chase_hip_convert_s2d", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
@@ -232,6 +239,28 @@ class Context:
         else:
             f = lib.chase_hip_gemm_sd_bf16x3 if split else lib.chase_hip_gemm_sd
             check(f(self.h, op, m, n, k, float(alpha), A, lda, B, ldb, float(beta), Cm, ldc), "gemm_sd")
+
+    def bf16x3_pack_bytes(self, m, k, cplx):
+        """Bytes of the packed bf16x3 image of an m x k operand (chase_hip_bf16x3_pack_bytes)."""
+        b = c_size_t()
+        check(lib.chase_hip_bf16x3_pack_bytes(int(cplx), m, k, C.byref(b)), "bf16x3_pack_bytes")
+        return b.value
+
+    def bf16x3_pack(self, m, k, A, lda, packed, cplx, src_f64=False):
+        """packed = the bf16x3 image of the m x k fp32 (src_f64: fp64) matrix at device address A; every byte is written."""
+        check(lib.chase_hip_bf16x3_pack(self.h, int(cplx), int(src_f64), m, k, A, lda, packed), "bf16x3_pack")
+
+    def bf16x3_pack_diag(self, n, H64, ldh, packed, cplx):
+        """The n diagonal entries of an n x n pack, from the fp64 H; nothing else of packed is written."""
+        check(lib.chase_hip_bf16x3_pack_diag(self.h, int(cplx), n, H64, ldh, packed), "bf16x3_pack_diag")
+
+    def gemm32p(self, m, n, k, alpha, packedA, B, ldb, beta, Cm, ldc, cplx):
+        """The bf16x3 product of gemm32(..., split=True) with A given as its pack (bf16x3_pack of the same m, k): same bits."""
+        if cplx:
+            check(lib.chase_hip_gemm_c_bf16x3p(self.h, m, n, k, _c2(alpha), packedA, B, ldb, _c2(beta), Cm, ldc), "gemm_c_bf16x3p")
+        else:
+            check(lib.chase_hip_gemm_s_bf16x3p(self.h, m, n, k, float(alpha), packedA, B, ldb, float(beta), Cm, ldc),
+                  "gemm_s_bf16x3p")
 
     def set_gemm_min_rounds(self, rounds):
         """chase_hip_ctx_set_gemm_min_rounds: > 0 while products share the chip with a collective (they are cut along K)."""

@@ -302,6 +302,70 @@ int chase_hip_gemm_c_bf16x3(chase_hip_ctx* c, char opA, int m, int n, int k, con
     return gemm32(c, true, opA, m, n, k, alpha, (const float*)A, lda, (const float*)B, ldb, beta, (float*)C, ldc, true);
 }
 
+// ---- the bf16x3 product on a packed A (gemm_mfma_bf16x3p.hip) ----
+int chase_hip_bf16x3_pack_bytes(int cplx, int m, int k, size_t* bytes)
+{
+    if (!bytes) return set_error(CHASE_HIP_EINVAL, "bf16x3_pack_bytes: bytes == NULL");
+    if (m < 0 || k < 0) return set_error(CHASE_HIP_EINVAL, "bf16x3_pack_bytes: negative dimension");
+    *bytes = bf16x3_pack_bytes(cplx != 0, m, k);
+    return 0;
+}
+
+int chase_hip_bf16x3_pack(chase_hip_ctx* c, int cplx, int src_f64, int m, int k, const void* A, long lda, void* packed)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "bf16x3_pack: NULL ctx");
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    if (c->oplog_on) c->oplog_add("bf16x3_pack", m, k, 0, 0);
+    if (m < 0 || k < 0 || lda < m) return set_error(CHASE_HIP_EINVAL, "bf16x3_pack: bad shape");
+    if (m == 0 || k == 0) return 0;
+    if (!A || !packed) return set_error(CHASE_HIP_EINVAL, "bf16x3_pack: NULL matrix");
+    if (((uintptr_t)packed & 15) != 0) return set_error(CHASE_HIP_EINVAL, "bf16x3_pack: packed must be 16-byte aligned");
+    int e = bf16x3_pack(c->stream, cplx != 0, src_f64 != 0, m, k, A, lda, packed);
+    if (e) return hip_fail((hipError_t)e, "bf16x3_pack launch");
+    return 0;
+}
+
+int chase_hip_bf16x3_pack_diag(chase_hip_ctx* c, int cplx, int n, const void* H64, long ldh, void* packed)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "bf16x3_pack_diag: NULL ctx");
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    if (c->oplog_on) c->oplog_add("bf16x3_pack_diag", n, 0, 0, 0);
+    if (n < 0 || ldh < n) return set_error(CHASE_HIP_EINVAL, "bf16x3_pack_diag: bad shape");
+    if (n == 0) return 0;
+    if (!H64 || !packed) return set_error(CHASE_HIP_EINVAL, "bf16x3_pack_diag: NULL argument");
+    int e = bf16x3_pack_diag(c->stream, cplx != 0, n, (const double*)H64, ldh, packed);
+    if (e) return hip_fail((hipError_t)e, "bf16x3_pack_diag launch");
+    return 0;
+}
+
+static int gemm32p(chase_hip_ctx* c, bool cplx, int m, int n, int k, const float* alpha, const void* packedA, const float* B, long ldb,
+                   const float* beta, float* C, long ldc)
+{
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    int rc = check_gemm('N', m, n, k, packedA, m, B, ldb, C, ldc);
+    if (rc || m == 0 || n == 0) return rc;
+    if (k > 0 && ((uintptr_t)packedA & 15) != 0) return set_error(CHASE_HIP_EINVAL, "gemm_bf16x3p: packedA must be 16-byte aligned");
+    if (c->oplog_on) c->oplog_add(cplx ? "gemm_c3pN" : "gemm_s3pN", m, n, k, c->phase * 100);
+    int e = gemm_bf16x3p(c->stream, cplx, m, n, k, alpha, packedA, B, ldb, beta, C, ldc, c->num_cu, c->phase == 1 ? 1 : 0);
+    if (e) return hip_fail((hipError_t)e, "gemm_bf16x3p launch");
+    return 0;
+}
+
+int chase_hip_gemm_s_bf16x3p(chase_hip_ctx* c, int m, int n, int k, float alpha, const void* packedA, const float* B, long ldb,
+                             float beta, float* C, long ldc)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "ctx == NULL");
+    return gemm32p(c, false, m, n, k, &alpha, packedA, B, ldb, &beta, C, ldc);
+}
+
+int chase_hip_gemm_c_bf16x3p(chase_hip_ctx* c, int m, int n, int k, const float alpha[2], const void* packedA, const void* B, long ldb,
+                             const float beta[2], void* C, long ldc)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "ctx == NULL");
+    if (!alpha || !beta) return set_error(CHASE_HIP_EINVAL, "gemm_c_bf16x3p: NULL alpha/beta");
+    return gemm32p(c, true, m, n, k, alpha, packedA, (const float*)B, ldb, beta, (float*)C, ldc);
+}
+
 // fp32 operands, fp64 result and scalars, op(A) = N or C: the filter product of the grid solver
 static int gemm32w(chase_hip_ctx* c, bool cplx, char opA, int m, int n, int k, const double* alpha, const float* A, long lda,
                    const float* B, long ldb, const double* beta, double* C, long ldc, bool split = false)

@@ -52,6 +52,14 @@ int gemm_bf16x3(hipStream_t st, bool cplx, char opA, int m, int n, int k, const 
 int gemm_bf16x3w(hipStream_t st, bool cplx, char opA, int m, int n, int k, const double* alpha, const float* A, long lda,
                  const float* B, long ldb, const double* beta, double* C, long ldc, int num_cu, int tag = 0, double* ws = nullptr,
                  size_t ws_bytes = 0, int min_rounds = 0, int* pieces = nullptr);
+// the narrow bf16x3 product with A split and tiled once (gemm_mfma_bf16x3p.hip): pack writes all pack_bytes(m, k) bytes of the
+// packed image of an m x k fp32 (src_f64: fp64, rounded to fp32 first) A, pack_diag the n diagonal entries of an n x n pack from
+// an fp64 H, and gemm_bf16x3p is gemm_bf16x3('N', ...) on the pack, bit for bit.
+size_t bf16x3_pack_bytes(bool cplx, int m, int k);
+int bf16x3_pack(hipStream_t st, bool cplx, bool src_f64, int m, int k, const void* A, long lda, void* packed);
+int bf16x3_pack_diag(hipStream_t st, bool cplx, int n, const double* H, long ldh, void* packed);
+int gemm_bf16x3p(hipStream_t st, bool cplx, int m, int n, int k, const float* alpha, const void* packedA, const float* B, long ldb,
+                 const float* beta, float* C, long ldc, int num_cu, int tag = 0);
 // C = alpha (S_0 + S_1 + ... + S_{sk-1}) + beta C in fp64, the slabs summed in index order (vec_kernels.hip): slab p is the dense
 // lds x (columns) block at S + p * slab_stride (doubles; lds in elements, even), of which rows < m and columns < n are read.
 // alpha / beta point to 1 (real) or 2 (complex) host doubles; beta == 0: C is not read.

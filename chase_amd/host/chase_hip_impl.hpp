@@ -76,6 +76,7 @@ public:
         alloc((void**)&dScal_, 4096);
         if (const char* e = std::getenv("CHASE_HIP_MIXED_PRECISION")) mixed_ = std::atoi(e) != 0;
         sp_split_ = sp_product_env() != 0;
+        sp_prepack_ = sp_prepack_env() != 0;
     }
     ~ChaseHip() override
     {
@@ -140,6 +141,7 @@ public:
             hip_ok(chase_hip_complete_hermitian(ctx_, CP, uplo, (int)N_, dH_, (long)ldd_h_), "complete_hermitian");
             hv_valid_ = false;
             hs_valid_ = false;
+            hp_valid_ = false;
             return;
         }
         const bool up = (uplo == 'U' || uplo == 'u');
@@ -150,6 +152,7 @@ public:
             }
         h_resident_ = false;
         hs_valid_ = false;
+        hp_valid_ = false;
     }
 
     // ---- solver life cycle -------------------------------------------------------------------------------------
@@ -228,6 +231,7 @@ public:
     {
         filter_ms_ = 0; hemm_calls_ = 0; hemm_reused_vecs_ = 0;
         hemm_sp_calls_ = 0; hemm_sp_vecs_ = 0; sp_filters_ = 0; hemm_sp_split_calls_ = 0;
+        hemm_sp_packed_calls_ = 0; sp_pack_full_ = 0; sp_pack_diag_ = 0;
     }
     std::size_t hemm_calls() const override { return hemm_calls_; }
     std::size_t hemm_reused_vecs() const override { return hemm_reused_vecs_; }
@@ -239,6 +243,11 @@ public:
     bool set_sp_product(int v) override { sp_split_ = v != 0; return true; }
     int sp_product() const override { return sp_split_ ? 1 : 0; }
     std::size_t hemm_sp_split_calls() const override { return hemm_sp_split_calls_; }
+    bool set_sp_prepack(int v) override { sp_prepack_ = v != 0; return true; }
+    int sp_prepack() const override { return sp_prepack_ ? 1 : 0; }
+    std::size_t hemm_sp_packed_calls() const override { return hemm_sp_packed_calls_; }
+    std::size_t sp_pack_full() const override { return sp_pack_full_; }
+    std::size_t sp_pack_diag() const override { return sp_pack_diag_; }
 
     // The filter brackets its products with Shift(-c) ... Shift(+c, true).  Mixed precision (chase_cpu.hpp:384-445): the decision
     // is taken here, once per filter call, from the residuals the driver left in resid_ (all max() before the first iteration).
@@ -288,10 +297,15 @@ public:
                     sp_synced_ = true;
                     ++sp_filters_;
                 }
-                gemm32(N_, ncols, N_, alpha, sH_, ld_s_, sV1_ + c0 * ld_s_, ld_s_, beta, sV2_ + c0 * ld_s_, ld_s_);
+                if (sp_packed_) {
+                    gemm32p(N_, ncols, N_, alpha, pH_, sV1_ + c0 * ld_s_, ld_s_, beta, sV2_ + c0 * ld_s_, ld_s_);
+                    ++hemm_sp_packed_calls_;
+                } else {
+                    gemm32(N_, ncols, N_, alpha, sH_, ld_s_, sV1_ + c0 * ld_s_, ld_s_, beta, sV2_ + c0 * ld_s_, ld_s_);
+                }
                 ++hemm_sp_calls_;
                 hemm_sp_vecs_ += ncols;
-                if (sp_split_) ++hemm_sp_split_calls_;
+                if (sp_split_ || sp_packed_) ++hemm_sp_split_calls_;
             } else {
                 gemm('N', N_, ncols, N_, alpha, dH_, ldd_h_, dV1_ + c0 * N_, N_, beta, dV2_ + c0 * N_, N_);
                 ++hemm_calls_;
@@ -481,23 +495,44 @@ protected:
             hip_ok(chase_hip_upload_matrix(ctx_, CP, (int)N_, (int)N_, H_, (long)ldh_, dH_, (long)ldd_h_), "upload H");
         h_resident_ = true;
         hs_valid_ = false;                  // the fp32 shadow belongs to the previous matrix
+        hp_valid_ = false;                  // and so does the packed bf16x3 image
     }
-    // a qualifying Shift(-c): the fp32 shadow of the (already shifted) H.  First time after H changed: the whole matrix;
-    // afterwards the off-diagonals are still right and only the diagonal follows the shift.
+    // a qualifying Shift(-c): the fp32 shadow (or, sp_prepack, the packed bf16x3 image) of the (already shifted) H.  First time
+    // after H changed: the whole matrix; afterwards the off-diagonals are still right and only the diagonal follows the shift.
     void begin_single_precision()
     {
-        if (!sH_) {
+        if (!sV1_) {
             ld_s_ = (N_ + 3) & ~(std::size_t)3;            // every shadow column starts on a 16-byte boundary
-            alloc((void**)&sH_, ld_s_ * N_ * sizeof(ST));
             alloc((void**)&sV1_, ld_s_ * nevex_ * sizeof(ST));
             alloc((void**)&sV2_, ld_s_ * nevex_ * sizeof(ST));
         }
         if (!h_resident_) upload_H();
-        if (!hs_valid_) {
-            hip_ok(chase_hip_convert_d2s(ctx_, CP, (int)N_, (int)N_, dH_, (long)ldd_h_, sH_, (long)ld_s_), "convert_d2s H");
-            hs_valid_ = true;
+        // sp_prepack with the bf16x3 product: H split into its bf16 parts and tiled once, straight from the shifted fp64 H (no
+        // fp32 shadow of H is made or kept for such calls); the two images are kept valid independently, so the keys may change
+        // between filter calls - either refresh rewrites the whole diagonal
+        sp_packed_ = sp_split_ && sp_prepack_;
+        if (sp_packed_) {
+            if (!pH_) {
+                std::size_t bytes = 0;
+                hip_ok(chase_hip_bf16x3_pack_bytes(CP, (int)N_, (int)N_, &bytes), "bf16x3_pack_bytes");
+                alloc(&pH_, bytes);
+            }
+            if (!hp_valid_) {
+                hip_ok(chase_hip_bf16x3_pack(ctx_, CP, 1, (int)N_, (int)N_, dH_, (long)ldd_h_, pH_), "bf16x3_pack H");
+                hp_valid_ = true;
+                ++sp_pack_full_;
+            } else {
+                hip_ok(chase_hip_bf16x3_pack_diag(ctx_, CP, (int)N_, dH_, (long)ldd_h_, pH_), "bf16x3_pack_diag");
+                ++sp_pack_diag_;
+            }
         } else {
-            hip_ok(chase_hip_diag_d2s(ctx_, CP, (int)N_, dH_, (long)ldd_h_, sH_, (long)ld_s_), "diag_d2s");
+            if (!sH_) alloc((void**)&sH_, ld_s_ * N_ * sizeof(ST));
+            if (!hs_valid_) {
+                hip_ok(chase_hip_convert_d2s(ctx_, CP, (int)N_, (int)N_, dH_, (long)ldd_h_, sH_, (long)ld_s_), "convert_d2s H");
+                hs_valid_ = true;
+            } else {
+                hip_ok(chase_hip_diag_d2s(ctx_, CP, (int)N_, dH_, (long)ldd_h_, sH_, (long)ld_s_), "diag_d2s");
+            }
         }
         sp_active_ = true;
         sp_synced_ = false;
@@ -510,6 +545,7 @@ protected:
                                          dV1_ + locked_ * N_, (long)N_), "convert_s2d");
         sp_active_ = false;
         sp_synced_ = false;
+        sp_packed_ = false;
     }
     void gemm32(std::size_t m, std::size_t n, std::size_t k, T alpha, const ST* A, std::size_t lda, const ST* B, std::size_t ldb,
                 T beta, ST* C, std::size_t ldc)
@@ -524,6 +560,19 @@ protected:
                                                                           (long)ldb, (float)beta, C, (long)ldc);
         }
         hip_ok(rc, "gemm32");
+    }
+    // the bf16x3 product on the packed H
+    void gemm32p(std::size_t m, std::size_t n, std::size_t k, T alpha, const void* packedA, const ST* B, std::size_t ldb, T beta,
+                 ST* C, std::size_t ldc)
+    {
+        int rc;
+        if constexpr (is_cplx<T>::value) {
+            const float a[2] = {(float)alpha.real(), (float)alpha.imag()}, b[2] = {(float)beta.real(), (float)beta.imag()};
+            rc = chase_hip_gemm_c_bf16x3p(ctx_, (int)m, (int)n, (int)k, a, packedA, B, (long)ldb, b, C, (long)ldc);
+        } else {
+            rc = chase_hip_gemm_s_bf16x3p(ctx_, (int)m, (int)n, (int)k, (float)alpha, packedA, B, (long)ldb, (float)beta, C, (long)ldc);
+        }
+        hip_ok(rc, "gemm32p");
     }
     void gemm(char op, std::size_t m, std::size_t n, std::size_t k, T alpha, const T* A, std::size_t lda, const T* B,
               std::size_t ldb, T beta, T* C, std::size_t ldc)
@@ -680,6 +729,10 @@ protected:
     ST *sH_ = nullptr, *sV1_ = nullptr, *sV2_ = nullptr;
     std::size_t ld_s_ = 0, hemm_sp_calls_ = 0, hemm_sp_vecs_ = 0, sp_filters_ = 0, hemm_sp_split_calls_ = 0;
     bool sp_split_ = false;                // sp_product = 1: the fp32 filter products run as bf16x3
+    bool sp_prepack_ = false;              // sp_prepack = 1: ... on H split and tiled once (pH_, valid while hp_valid_)
+    bool sp_packed_ = false, hp_valid_ = false;        // this filter call runs on pH_
+    void* pH_ = nullptr;
+    std::size_t hemm_sp_packed_calls_ = 0, sp_pack_full_ = 0, sp_pack_diag_ = 0;
 };
 
 } // namespace chase_amd

@@ -48,10 +48,13 @@ public:
         mixed_precision_env_ignored("the pseudo-Hermitian solver");
         this->sp_split_ = false;
         sp_product_env_ignored("the pseudo-Hermitian solver");
+        this->sp_prepack_ = false;
+        sp_prepack_env_ignored("the pseudo-Hermitian solver");
     }
 
     bool set_mixed_precision(bool on) override { return !on; }
     bool set_sp_product(int v) override { return v == 0; }
+    bool set_sp_prepack(int v) override { return v == 0; }
     bool isSym() override { return false; }
     bool isPseudoHerm() override { return true; }
     bool checkSymmetryEasy() override { return false; }

@@ -29,6 +29,13 @@ struct HipImplExtras {
     virtual bool set_sp_product(int v) { return v == 0; }
     virtual int sp_product() const { return 0; }
     virtual std::size_t hemm_sp_split_calls() const { return 0; }   // fp32 filter products that ran as bf16x3
+    // sp_prepack: a single-precision filter call that runs bf16x3 (sp_product = 1) takes H split and tiled once
+    // (chase_hip_gemm_*_bf16x3p) - the same bits; inert otherwise.  false = this Impl does not have it and v != 0 was not taken
+    virtual bool set_sp_prepack(int v) { return v == 0; }
+    virtual int sp_prepack() const { return 0; }
+    virtual std::size_t hemm_sp_packed_calls() const { return 0; }  // the hemm_sp_split_calls that ran on the packed H
+    virtual std::size_t sp_pack_full() const { return 0; }          // whole-matrix packs of H
+    virtual std::size_t sp_pack_diag() const { return 0; }          // diagonal refreshes of the pack
     virtual void set_device_rng(bool) = 0;
     virtual void reset_counters() = 0;
     virtual void* device_V1() = 0;               // current (local) vector block, pending swaps applied
@@ -73,6 +80,19 @@ inline void sp_product_env_ignored(const char* impl)
     static std::atomic<bool> said{false};
     if (sp_product_env() == 0 || said.exchange(true)) return;
     std::fprintf(stderr, "chase_hip: CHASE_HIP_SP_PRODUCT is ignored by %s (Hermitian solvers only)\n", impl);
+}
+
+// CHASE_HIP_SP_PREPACK=1: the construction-time default of sp_prepack
+inline int sp_prepack_env()
+{
+    const char* e = std::getenv("CHASE_HIP_SP_PREPACK");
+    return e && std::atoi(e) != 0 ? 1 : 0;
+}
+inline void sp_prepack_env_ignored(const char* impl)
+{
+    static std::atomic<bool> said{false};
+    if (sp_prepack_env() == 0 || said.exchange(true)) return;
+    std::fprintf(stderr, "chase_hip: CHASE_HIP_SP_PREPACK is ignored by %s (single-GPU Hermitian solver only)\n", impl);
 }
 
 } // namespace chase_amd

@@ -77,6 +77,7 @@ public:
         if (N == 0 || nevex_ == 0 || nc_ > N) throw std::invalid_argument("pChaseHip: need 0 < nev+nex <= N");
         if (const char* e = std::getenv("CHASE_HIP_MIXED_PRECISION")) mixed_ = std::atoi(e) != 0;   // (the pseudo Impl clears it)
         sp_split_ = sp_product_env() != 0;                                                         // (and this)
+        sp_prepack_env_ignored("the grid solvers");            // (op C and the fp64 epilogue from a packed block: not built)
         hip_ok(chase_hip_grid_info(grid, &nprow_, &npcol_, &myrow_, &mycol_), "grid_info");
         Rr_.N = Cc_.N = (long)N;
         Rr_.p = nprow_; Rr_.q = myrow_; Cc_.p = npcol_; Cc_.q = mycol_;

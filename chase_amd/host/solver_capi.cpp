@@ -215,6 +215,13 @@ int chase_hip_solver_set(chase_hip_solver* s, const char* key, double v)
                 rc = chase_hip::set_error(CHASE_HIP_EINVAL, "solver_set: sp_product = 1 exists on the Hermitian solvers only, "
                                                             "single GPU and grid (the pseudo-Hermitian solvers filter in fp64)");
         }
+        else if (name == "sp_prepack") {
+            if (v != 0.0 && v != 1.0)
+                rc = chase_hip::set_error(CHASE_HIP_EINVAL, "solver_set: sp_prepack is 0 or 1");
+            else if (!s->ex->set_sp_prepack((int)v))
+                rc = chase_hip::set_error(CHASE_HIP_EINVAL, "solver_set: sp_prepack = 1 exists on the single-GPU Hermitian solver only "
+                                                            "(the grid and the pseudo-Hermitian solvers do not pack H)");
+        }
         else if (name == "reset_counters") s->ex->reset_counters();
         else rc = chase_hip::set_error(CHASE_HIP_EINVAL, "solver_set: unknown key");
     }); });
@@ -257,6 +264,10 @@ int chase_hip_solver_get(chase_hip_solver* s, const char* key, double* out)
         else if (name == "sp_filters") *out = (double)s->ex->sp_filters();
         else if (name == "sp_product") *out = (double)s->ex->sp_product();
         else if (name == "hemm_sp_split_calls") *out = (double)s->ex->hemm_sp_split_calls();
+        else if (name == "sp_prepack") *out = (double)s->ex->sp_prepack();
+        else if (name == "hemm_sp_packed_calls") *out = (double)s->ex->hemm_sp_packed_calls();
+        else if (name == "sp_pack_full") *out = (double)s->ex->sp_pack_full();
+        else if (name == "sp_pack_diag") *out = (double)s->ex->sp_pack_diag();
         else if (name == "resd_rechecked") *out = (double)s->ex->resd_rechecked();
         else if (name == "tape_qr_mismatches") *out = (double)s->tape.qr_variant_mismatches;   // of the last replay
         else if (name == "tape_qr_retries") *out = (double)s->ex->forced_qr_retries();   // shifted re-factorisations, replay

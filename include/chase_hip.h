@@ -118,6 +118,31 @@ int chase_hip_gemm_sd_bf16x3(chase_hip_ctx* ctx, char opA, int m, int n, int k, 
 int chase_hip_gemm_cz_bf16x3(chase_hip_ctx* ctx, char opA, int m, int n, int k, const double alpha[2], const void* A, long lda,
                              const void* B, long ldb, const double beta[2], void* C, long ldc);
 
+/* The narrow bf16x3 product with A split and tiled once ("packed"): for an A that stays while B changes - the filter's H.
+ * Layout of the packed image of an m x k A (real fp32, or interleaved complex fp32): rows are padded to P = ceil(m / 128) panels
+ * of 128, k to T = ceil(k / 16) steps of 16.  Block (panel p, step t) starts at byte ((p T + t) planes 256) 16, the step fastest;
+ * planes = 3 (real) or 6 (complex: re p1, p2, p3, then im p1, p2, p3), each plane 256 pieces of 16 bytes.  Piece (row, h),
+ * row < 128, h < 2, of plane s sits at piece index 2 row + (h ^ bit 2 of row ^ bit 3 of row) of that plane and holds the eight
+ * bf16 numbers x_s[128 p + row, 16 t + 8 h + 0..7] in ascending k, where x = x1 + x2 + x3, x1 = bf16(x), x2 = bf16(x - x1),
+ * x3 = bf16(x - x1 - x2), round to nearest even (the split of the _bf16x3 products).  Padding rows and k are zero bytes.
+ * pack_bytes: the size, P T planes 4096 (6 bytes per padded real element; 0 when m or k is 0).
+ * pack: writes EVERY byte of the image (no caller clears it); src_f64 = 0: A is fp32 / complex fp32, src_f64 = 1: fp64 /
+ *   complex fp64, each component rounded to fp32 (nearest even, as convert_d2s) and then split; any lda >= m and any base the
+ *   element type allows; packed 16-byte aligned; m == 0 or k == 0: nothing is done.
+ * pack_diag: the n diagonal entries of an n x n pack from the fp64 H, nothing else is written: after it the image is byte
+ *   for byte a pack of H (the contract diag_d2s has for the fp32 shadow).
+ * gemm_s_bf16x3p / gemm_c_bf16x3p: C = alpha A B + beta C with A given as pack(A) of exactly this m and k, op(A) = N, fp32
+ *   B, C and scalars: bit for bit chase_hip_gemm_s_bf16x3 / _c_bf16x3('N', ...) on the unpacked operands, for every shape,
+ *   leading dimension, alpha and beta (same tiles, same six MFMAs per 16 k in the same order).  beta == 0: C is not read;
+ *   k == 0: C = beta C.  Operator-log names bf16x3_pack, bf16x3_pack_diag, gemm_s3pN, gemm_c3pN. */
+int chase_hip_bf16x3_pack_bytes(int cplx, int m, int k, size_t* bytes);
+int chase_hip_bf16x3_pack(chase_hip_ctx* ctx, int cplx, int src_f64, int m, int k, const void* A, long lda, void* packed);
+int chase_hip_bf16x3_pack_diag(chase_hip_ctx* ctx, int cplx, int n, const void* H64, long ldh, void* packed);
+int chase_hip_gemm_s_bf16x3p(chase_hip_ctx* ctx, int m, int n, int k, float alpha, const void* packedA, const float* B, long ldb,
+                             float beta, float* C, long ldc);
+int chase_hip_gemm_c_bf16x3p(chase_hip_ctx* ctx, int m, int n, int k, const float alpha[2], const void* packedA, const void* B,
+                             long ldb, const float beta[2], void* C, long ldc);
+
 /* The launch chase_hip_gemm_sd / _cz (bf16x3 != 0: their _bf16x3 twins) make for a product on a device with num_cu compute units
  * while the context's gemm_min_rounds is min_rounds, without making it (host-only: callable without a GPU; a pure function of
  * its arguments).  gm x gn tiles of 128 x bn; sk K pieces per tile of kchunk k each (a multiple of 16; the last piece takes the

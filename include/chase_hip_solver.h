@@ -69,7 +69,16 @@ int chase_hip_solver_destroy(chase_hip_solver* s);
  * mixed_precision has put it into single precision - 0 the fp32 MFMA (chase_hip_gemm_s / _c / _sd / _cz), 1 the bf16x3 split
  * product on the bf16 matrix cores (chase_hip_gemm_*_bf16x3).  The 1e-3 rule, the shadows, the conversions and the counters above
  * are untouched, and with mixed_precision = 0 the key has no effect.  get additionally: hemm_sp_split_calls (the hemm_sp_calls
- * that ran as bf16x3; cleared by reset_counters). */
+ * that ran as bf16x3; cleared by reset_counters).
+ * sp_prepack (set and get, 0 | 1 - anything else CHASE_HIP_EINVAL; default 0 or CHASE_HIP_SP_PREPACK=1 at construction; the
+ * single-GPU Hermitian solver only - 1 on a grid or a pseudo-Hermitian solver returns CHASE_HIP_EINVAL, and they say once on
+ * stderr that the environment variable is ignored): a filter call that mixed_precision has put into single precision AND that
+ * runs sp_product = 1 takes H split into its three bf16 parts and tiled once (chase_hip_bf16x3_pack, straight from the shifted
+ * fp64 H: such calls make and keep no fp32 shadow of H; 6 instead of 4 bytes per real element) and multiplies with
+ * chase_hip_gemm_*_bf16x3p - the bits of sp_product = 1 without it.  The first such call after H changed packs the whole
+ * matrix, later ones refresh the diagonal (chase_hip_bf16x3_pack_diag).  In every other filter call the key is inert.  get
+ * additionally: hemm_sp_packed_calls (the hemm_sp_split_calls that ran on the packed H), sp_pack_full (whole-matrix packs),
+ * sp_pack_diag (diagonal refreshes); cleared by reset_counters. */
 int chase_hip_solver_set(chase_hip_solver* s, const char* key, double value);
 int chase_hip_solver_get(chase_hip_solver* s, const char* key, double* value);
 int chase_hip_solver_solve(chase_hip_solver* s, int record_trace);
