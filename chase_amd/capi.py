@@ -88,6 +88,7 @@ _sig("chase_hip_diag_list_d2s", c_int, c_void_p, c_int, c_void_p, c_long, c_void
 _sig("chase_hip_convert_d2s", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
 _sig("chase_hip_convert_s2d", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
 _sig("chase_hip_diag_d2s", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_axpy_sp", c_int, c_void_p, c_int, c_int, c_int, P(C.c_float), c_void_p, c_long, c_void_p, c_long)
 _sig("chase_hip_mfma_f64_peak", c_int, c_void_p, P(c_double))
 _sig("chase_hip_gemm3m_enabled", c_int)
 _sig("chase_hip_host_lapack_warmup", c_int)
@@ -288,6 +289,10 @@ class Context:
         """Hs[i, i] (fp32) = H[i, i] (fp64) for i < n; nothing else of Hs is written."""
         check(lib.chase_hip_diag_d2s(self.h, int(cplx), n, H, ldh, Hs, ldhs), "diag_d2s")
 
+    def axpy_sp(self, m, n, gamma, X, ldx, Y, ldy, cplx):
+        """Y_j += gamma X_j on m x n fp32 / complex fp32 columns; device addresses, leading dimensions in elements."""
+        check(lib.chase_hip_axpy_sp(self.h, int(cplx), m, n, _c2(gamma), X, ldx, Y, ldy), "axpy_sp")
+
     def to_single(self, dA):
         """fp32 / complex fp32 copy of an fp64 / complex fp64 DeviceArray, converted on the device."""
         cplx = dA.dtype == np.complex128
@@ -438,6 +443,7 @@ _sig("chase_hip_op_end", c_int, c_void_p)
 _sig("chase_hip_op_initvecs", c_int, c_void_p, c_int)
 _sig("chase_hip_op_reinit_columns", c_int, c_void_p, c_size_t, P(c_size_t), c_size_t)
 _sig("chase_hip_op_shift", c_int, c_void_p, c_double, c_int)
+_sig("chase_hip_op_filter_phase", c_int, c_void_p, c_int)
 _sig("chase_hip_op_hemm", c_int, c_void_p, c_size_t, P(c_double), P(c_double), c_size_t, c_size_t)
 _sig("chase_hip_op_qr", c_int, c_void_p, c_size_t, c_double)
 _sig("chase_hip_op_rr", c_int, c_void_p, c_void_p, c_size_t)
@@ -638,6 +644,8 @@ class Solver:
         a = (c_size_t * len(cols))(*cols)
         check(lib.chase_hip_op_reinit_columns(self.h, fixednev, a, len(cols)), "ReinitColumns")
     def Shift(self, c, isunshift=False): check(lib.chase_hip_op_shift(self.h, float(c), int(isunshift)), "Shift")
+    def FilterPhaseStart(self): check(lib.chase_hip_op_filter_phase(self.h, 1), "FilterPhaseStart")
+    def FilterPhaseEnd(self): check(lib.chase_hip_op_filter_phase(self.h, 0), "FilterPhaseEnd")
 
     def HEMM(self, block, alpha, beta, offset_left, offset_right=0):
         check(lib.chase_hip_op_hemm(self.h, block, _z2(alpha), _z2(beta), offset_left, offset_right), "HEMM")
@@ -690,18 +698,24 @@ _sig("chase_hip_solver_lanczos_for_h2", c_int, c_void_p, c_int, c_int, P(c_doubl
 class PseudoSolver(Solver):
     """ChaseHipPseudo<T>: pseudo-Hermitian (BSE) Impl — subspace of 2*(nev+nex) columns, chase::Solve_pseudo."""
 
-    def __init__(self, ctx, H, nev, nex):
-        assert H.flags.f_contiguous and H.shape[0] == H.shape[1]
+    def __init__(self, ctx, H, nev, nex, h_on_device_ptr=None, N=None, cplx=None):
+        """H: the host matrix, or None with h_on_device_ptr, N and cplx: the matrix already lives in HBM and is used in place."""
         self.ctx, self.H = ctx, H
-        self.cplx = bool(np.iscomplexobj(H))
-        self.N, self.nev, self.nex = H.shape[0], nev, nex
+        if h_on_device_ptr is None:
+            assert H.flags.f_contiguous and H.shape[0] == H.shape[1]
+            self.cplx, self.N = bool(np.iscomplexobj(H)), H.shape[0]
+            hptr, on_dev = H.ctypes.data, 0
+        else:
+            self.cplx, self.N = bool(cplx), int(N)
+            hptr, on_dev = h_on_device_ptr, 1
+        self.nev, self.nex = nev, nex
         dt = np.complex128 if self.cplx else np.float64
         self.ncol = 2 * (nev + nex)
         self.V = np.zeros((self.N, self.ncol), dtype=dt, order="F")
         self.ritzv = np.zeros(self.ncol)
         h = c_void_p()
-        check(lib.chase_hip_solver_create_pseudo(C.byref(h), ctx.h, int(self.cplx), self.N, nev, nex, H.ctypes.data,
-                                                 self.N, self.V.ctypes.data, self.N, self.ritzv.ctypes.data, 0),
+        check(lib.chase_hip_solver_create_pseudo(C.byref(h), ctx.h, int(self.cplx), self.N, nev, nex, hptr,
+                                                 self.N, self.V.ctypes.data, self.N, self.ritzv.ctypes.data, on_dev),
               "solver_create_pseudo")
         self.h = h
 

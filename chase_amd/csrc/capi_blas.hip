@@ -317,6 +317,20 @@ int chase_hip_convert_s2d(chase_hip_ctx* c, int cplx, int m, int n, const void* 
     return 0;
 }
 
+int chase_hip_axpy_sp(chase_hip_ctx* c, int cplx, int m, int n, const float* gamma, const void* X, long ldx, void* Y, long ldy)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "axpy_sp: NULL ctx");
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    if (c->oplog_on) c->oplog_add("axpy_sp", m, n, 0, 0);
+    if (m < 0 || n < 0 || ldx < m || ldy < m) return set_error(CHASE_HIP_EINVAL, "axpy_sp: bad shape");
+    if (m == 0 || n == 0) return 0;
+    if (!gamma || !X || !Y) return set_error(CHASE_HIP_EINVAL, "axpy_sp: NULL argument");
+    const int e = ept_of(cplx);
+    KCHK(axpy_sp(c->stream, cplx != 0, gamma[0], cplx ? gamma[1] : 0.0f, (const float*)X, ldx * e, (float*)Y, ldy * e, (long)m * e, n),
+         "axpy_sp");
+    return 0;
+}
+
 int chase_hip_diag_d2s(chase_hip_ctx* c, int cplx, int n, const void* H, long ldh, void* Hs, long ldhs)
 {
     if (!c || ((!H || !Hs) && n > 0)) return set_error(CHASE_HIP_EINVAL, "diag_d2s: NULL argument");

@@ -107,6 +107,8 @@ int mirror_lower(hipStream_t st, double* A, long lda, int n, int ept, int zero_d
 int convert_d2s(hipStream_t st, const double* src, long ld_src, float* dst, long ld_dst, long ms, int ncols);   // round to nearest
 int convert_s2d(hipStream_t st, const float* src, long ld_src, double* dst, long ld_dst, long ms, int ncols);   // exact
 int diag_d2s(hipStream_t st, const double* H, long ldh, float* Hs, long ldhs, int n, int ept);                  // Hs[i,i] = (float)H[i,i]
+// Y_j += (gr + i gi) X_j on fp32 columns of ms floats (m * ept), leading dimensions in floats; gamma by value
+int axpy_sp(hipStream_t st, bool cplx, float gr, float gi, const float* X, long ldx_f, float* Y, long ldy_f, long ms, int ncols);
 // Hs[rows[i], cols[i]] = (float)H[rows[i], cols[i]], i < cnt (device lists: the diagonal inside a rank's block)
 int diag_list_d2s(hipStream_t st, const double* H, long ldh, float* Hs, long ldhs, const int* rows, const int* cols, int cnt, int ept);
 

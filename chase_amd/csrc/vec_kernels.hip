@@ -206,6 +206,42 @@ __global__ __launch_bounds__(256) void convert_s2d_kernel(const float* __restric
         for (long i = 4 * n4 + (long)blockIdx.x * 256 + threadIdx.x; i < ms; i += (long)gridDim.x * 256) d[i] = (double)s[i];
     }
 }
+// Y_j += gamma X_j on fp32 / complex fp32 columns: the gamma term of the single-precision H^2 filter step.  gamma travels in the
+// kernel arguments (no device-side scalar); ms floats per column (complex: (re, im) pairs); 16 bytes per access where vec says
+// that base pointers and leading dimensions allow, the rest of a column - or all of it - element by element.  X and Y are
+// distinct buffers.  Streaming: 3 ms ncols floats.
+template <bool CPLX>
+__global__ __launch_bounds__(256) void axpy_sp_kernel(float gr, float gi, const float* __restrict__ X, long ldx_f,
+                                                      float* __restrict__ Y, long ldy_f, long ms, int ncols, int vec)
+{
+    constexpr int E = CPLX ? 2 : 1;
+    for (int j = blockIdx.y; j < ncols; j += gridDim.y) {
+        const float* x = X + (long)j * ldx_f;
+        float* y = Y + (long)j * ldy_f;
+        const long n4 = vec ? (ms >> 2) : 0;
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+            const float4 a = ((const float4*)x)[i];
+            float4 b = ((float4*)y)[i];
+            if (CPLX) {
+                b.x += gr * a.x - gi * a.y; b.y += gr * a.y + gi * a.x;
+                b.z += gr * a.z - gi * a.w; b.w += gr * a.w + gi * a.z;
+            } else {
+                b.x += gr * a.x; b.y += gr * a.y; b.z += gr * a.z; b.w += gr * a.w;
+            }
+            ((float4*)y)[i] = b;
+        }
+        const long ne = ms / E;                                  // elements of a column; 4 n4 is a multiple of E
+        for (long i = 4 * n4 / E + (long)blockIdx.x * 256 + threadIdx.x; i < ne; i += (long)gridDim.x * 256) {
+            if (CPLX) {
+                const float xr = x[2 * i], xi = x[2 * i + 1];
+                y[2 * i] += gr * xr - gi * xi;
+                y[2 * i + 1] += gr * xi + gi * xr;
+            } else {
+                y[i] += gr * x[i];
+            }
+        }
+    }
+}
 // The sum of the K pieces of a wide single-precision product (gemm_sp_frame.h): C = alpha (S_0 + S_1 + ... + S_{sk-1}) + beta C
 // in fp64, piece after piece in index order - one fixed order per element.  Slab p is the dense block at S + p * stride (lds_d
 // doubles per column, 16-byte aligned columns: always read 16 bytes wide; up to five of these loads are in flight per lane);
@@ -596,6 +632,14 @@ int convert_s2d(hipStream_t st, const float* src, long ld_src, double* dst, long
     if (ms <= 0 || ncols <= 0) return 0;
     const int vec = ((ld_src & 3) == 0) && ((ld_dst & 1) == 0) && (((uintptr_t)src & 15) == 0) && (((uintptr_t)dst & 15) == 0);
     hipLaunchKernelGGL(convert_s2d_kernel, grid2(ms, ncols), dim3(256), 0, st, src, ld_src, dst, ld_dst, ms, ncols, vec);
+    return (int)hipGetLastError();
+}
+int axpy_sp(hipStream_t st, bool cplx, float gr, float gi, const float* X, long ldx_f, float* Y, long ldy_f, long ms, int ncols)
+{
+    if (ms <= 0 || ncols <= 0) return 0;
+    const int vec = ((ldx_f & 3) == 0) && ((ldy_f & 3) == 0) && (((uintptr_t)X & 15) == 0) && (((uintptr_t)Y & 15) == 0);
+    if (cplx) hipLaunchKernelGGL(axpy_sp_kernel<true>, grid2(ms, ncols), dim3(256), 0, st, gr, gi, X, ldx_f, Y, ldy_f, ms, ncols, vec);
+    else      hipLaunchKernelGGL(axpy_sp_kernel<false>, grid2(ms, ncols), dim3(256), 0, st, gr, gi, X, ldx_f, Y, ldy_f, ms, ncols, vec);
     return (int)hipGetLastError();
 }
 int sp_slab_reduce(hipStream_t st, bool cplx, int m, int n, int sk, const double* S, long lds, long slab_stride, const double* alpha,

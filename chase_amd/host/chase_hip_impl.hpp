@@ -497,12 +497,14 @@ protected:
         hs_valid_ = false;                  // the fp32 shadow belongs to the previous matrix
         hp_valid_ = false;                  // and so does the packed bf16x3 image
     }
+    // leading dimension of the fp32 shadows: every shadow column starts on a 16-byte boundary
+    static std::size_t shadow_ld(std::size_t n) { return (n + 3) & ~(std::size_t)3; }
     // a qualifying Shift(-c): the fp32 shadow (or, sp_prepack, the packed bf16x3 image) of the (already shifted) H.  First time
     // after H changed: the whole matrix; afterwards the off-diagonals are still right and only the diagonal follows the shift.
     void begin_single_precision()
     {
         if (!sV1_) {
-            ld_s_ = (N_ + 3) & ~(std::size_t)3;            // every shadow column starts on a 16-byte boundary
+            ld_s_ = shadow_ld(N_);
             alloc((void**)&sV1_, ld_s_ * nevex_ * sizeof(ST));
             alloc((void**)&sV2_, ld_s_ * nevex_ * sizeof(ST));
         }

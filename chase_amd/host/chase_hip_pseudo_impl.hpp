@@ -11,11 +11,17 @@
 //   Lanczos (S inner product)   linalg/internal/cpu/lanczos.hpp:302-470
 // Everything that is plumbing of the sequential Impl (getters, life cycle, filter timing, deferred Swap, ReinitColumns,
 // LanczosDos, recompute_residuals, the CholQR / Householder choice, allocation) is inherited from ChaseHip with a vector
-// block of 2*(nev+nex) columns; its Hermitian-only state (cached H V, fp32 shadows, residual re-check) is never switched on.
+// block of 2*(nev+nex) columns; its Hermitian-only state (cached H V, residual re-check, the mixed_precision switch and its
+// bf16x3 products) is never switched on.
+// Mixed precision has a key of its own here, h2_mixed_precision / CHASE_HIP_H2_MIXED_PRECISION=1, default off (the reference's
+// CHASE_ENABLE_MIXED_PRECISION does nothing for pseudo-Hermitian matrices): an H^2 filter call that starts while the smallest
+// residual of the unlocked wanted pairs is above 1e-3 runs its steps in fp32 on the inherited shadows.  H^2 carries its shift in
+// gamma, so H never moves: its shadow is converted once per resident matrix.  Only the unlocked first-half columns enter fp32.
 // Column layout of the vector block: [locked | first half (unconverged) | second half (unconverged) | locked].
 // All O(N n) / O(N^2 n) work runs in the gfx950 kernels through the C ABI; the (2 nevex)^2 dense core of the
 // Rayleigh-Ritz step (potrf, three trsm, heevd) runs on the host like the reference CPU path.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <cstring>
@@ -32,8 +38,12 @@ class ChaseHipPseudo : public ChaseHip<T, BaseT, ConfigT> {
     using P::dH_; using P::ldd_h_; using P::dV1_; using P::dV2_; using P::dA_; using P::dScal_;
     using P::lanczosIter_; using P::numLanczos_; using P::hemm_calls_;
     using P::gemm; using P::flush_swaps; using P::qr_block;
+    using P::nev_; using P::sH_; using P::sV1_; using P::sV2_; using P::ld_s_; using P::hs_valid_; using P::h_resident_;
+    using P::sp_active_; using P::sp_synced_; using P::hemm_sp_calls_; using P::hemm_sp_vecs_; using P::sp_filters_;
+    using P::gemm32; using P::upload_H; using P::shadow_ld;
 public:
     using R = Base<T>;
+    using ST = typename P::ST;
     using P::CP;
     static constexpr int E = CP ? 2 : 1;
 
@@ -50,11 +60,16 @@ public:
         sp_product_env_ignored("the pseudo-Hermitian solver");
         this->sp_prepack_ = false;
         sp_prepack_env_ignored("the pseudo-Hermitian solver");
+        h2_mixed_ = h2_mixed_precision_env() != 0;
     }
 
     bool set_mixed_precision(bool on) override { return !on; }
     bool set_sp_product(int v) override { return v == 0; }
     bool set_sp_prepack(int v) override { return v == 0; }
+    bool set_h2_mixed_precision(bool on) override { h2_mixed_ = on; return true; }
+    bool h2_mixed_precision() const override { return h2_mixed_; }
+    std::size_t sp_h_converts() const override { return sp_h_converts_; }
+    void reset_counters() override { P::reset_counters(); sp_h_converts_ = 0; }
     bool isSym() override { return false; }
     bool isPseudoHerm() override { return true; }
     bool checkSymmetryEasy() override { return false; }
@@ -66,6 +81,20 @@ public:
         throw std::logic_error("ChaseHipPseudo: the pseudo-Hermitian filter uses HEMM_H2");
     }
 
+    // The filter call's bracket: the mixed-precision decision is taken at its start, once per call, from the residuals the driver
+    // left in resid_ (all max() before the first iteration) - the Hermitian Impl's rule, which decides in Shift
+    void FilterPhaseStart() override
+    {
+        P::FilterPhaseStart();
+        if (h2_mixed_ && locked_ < nev_ && *std::min_element(resid_.begin() + locked_, resid_.begin() + nev_) > (R)1e-3)
+            h2_begin_single_precision();
+    }
+    void FilterPhaseEnd() override
+    {
+        if (sp_active_) h2_end_single_precision();               // inside the timed phase: the conversions are filter time
+        P::FilterPhaseEnd();
+    }
+
     void HEMM_H2(std::size_t block, T alpha, T beta, T gamma, std::size_t offset_left, std::size_t offset_right = 0) override
     {
         flush_swaps();
@@ -74,18 +103,22 @@ public:
             const std::size_t c0 = offset_left + locked_;
             // the reference's filter call runs `block` columns from c0, i.e. past the first half into second-half columns
             // that ApplyKconjugate overwrites right after the filter (algorithm.inc:1012-1064): stop at the first half
-            if (c0 >= nevex_) { std::swap(dV1_, dV2_); return; }
+            if (c0 >= nevex_) { swap_buffers(); return; }
             if (c0 + ncols > nevex_) ncols = nevex_ - c0;
-            T* v1 = dV1_ + c0 * N_;
-            T* v2 = dV2_ + c0 * N_;
-            gemm('N', N_, ncols, N_, T(1), dH_, ldd_h_, v1, N_, T(0), dTmp_, N_);
-            gemm('N', N_, ncols, N_, alpha, dH_, ldd_h_, dTmp_, N_, beta, v2, N_);
-            upload_scalar(gamma);
-            hip_ok(chase_hip_col_axpy(ctx_, CP, (int)N_, (int)ncols, (const double*)dScal_, 0, 0, 1.0, v1, (long)N_, v2,
-                                      (long)N_), "axpy gamma");
-            hemm_calls_ += 2;
+            if (sp_active_) {
+                h2_step_single_precision(c0, ncols, alpha, beta, gamma);
+            } else {
+                T* v1 = dV1_ + c0 * N_;
+                T* v2 = dV2_ + c0 * N_;
+                gemm('N', N_, ncols, N_, T(1), dH_, ldd_h_, v1, N_, T(0), dTmp_, N_);
+                gemm('N', N_, ncols, N_, alpha, dH_, ldd_h_, dTmp_, N_, beta, v2, N_);
+                upload_scalar(gamma);
+                hip_ok(chase_hip_col_axpy(ctx_, CP, (int)N_, (int)ncols, (const double*)dScal_, 0, 0, 1.0, v1, (long)N_, v2,
+                                          (long)N_), "axpy gamma");
+                hemm_calls_ += 2;
+            }
         }
-        std::swap(dV1_, dV2_);
+        swap_buffers();
     }
 
     void ApplyKconjugate(std::size_t block) override
@@ -193,6 +226,64 @@ private:
         if (ldh < N || ldv < N) throw std::invalid_argument("ChaseHipPseudo: leading dimension smaller than N");
         return ctx;
     }
+    void swap_buffers()
+    {
+        std::swap(dV1_, dV2_);
+        if (sp_active_) std::swap(sV1_, sV2_);                // the shadows follow their buffers
+    }
+    // a qualifying filter call: shadows of the first half's nevex_ columns, allocated on first use, and fp32(H) - converted once
+    // per resident matrix (upload_H invalidates it); there is no shift to follow
+    void h2_begin_single_precision()
+    {
+        if (!sV1_) {
+            ld_s_ = shadow_ld(N_);
+            this->alloc((void**)&sV1_, ld_s_ * nevex_ * sizeof(ST));
+            this->alloc((void**)&sV2_, ld_s_ * nevex_ * sizeof(ST));
+            this->alloc((void**)&sTmp_, ld_s_ * nevex_ * sizeof(ST));
+            this->alloc((void**)&sH_, ld_s_ * N_ * sizeof(ST));
+        }
+        if (!h_resident_) upload_H();
+        if (!hs_valid_) {
+            hip_ok(chase_hip_convert_d2s(ctx_, CP, (int)N_, (int)N_, dH_, (long)ldd_h_, sH_, (long)ld_s_), "convert_d2s H");
+            hs_valid_ = true;
+            ++sp_h_converts_;
+        }
+        sp_active_ = true;
+        sp_synced_ = false;
+    }
+    // V2 = alpha H (H V1) + beta V2 + gamma V1 on the shadows, columns [c0, c0 + ncols) of the first half
+    void h2_step_single_precision(std::size_t c0, std::size_t ncols, T alpha, T beta, T gamma)
+    {
+        if (!sp_synced_) {
+            // the vectors enter fp32 right before the first fp32 product: unlocked first-half columns of both buffers
+            const std::size_t sub = nevex_ - locked_;
+            hip_ok(chase_hip_convert_d2s(ctx_, CP, (int)N_, (int)sub, dV1_ + locked_ * N_, (long)N_, sV1_ + locked_ * ld_s_,
+                                         (long)ld_s_), "convert_d2s");
+            hip_ok(chase_hip_convert_d2s(ctx_, CP, (int)N_, (int)sub, dV2_ + locked_ * N_, (long)N_, sV2_ + locked_ * ld_s_,
+                                         (long)ld_s_), "convert_d2s");
+            sp_synced_ = true;
+            ++sp_filters_;
+        }
+        ST* v1 = sV1_ + c0 * ld_s_;
+        ST* v2 = sV2_ + c0 * ld_s_;
+        ST* tmp = sTmp_ + c0 * ld_s_;
+        gemm32(N_, ncols, N_, T(1), sH_, ld_s_, v1, ld_s_, T(0), tmp, ld_s_);
+        gemm32(N_, ncols, N_, alpha, sH_, ld_s_, tmp, ld_s_, beta, v2, ld_s_);
+        const float g[2] = {(float)std::real(gamma), (float)std::imag(gamma)};
+        hip_ok(chase_hip_axpy_sp(ctx_, CP, (int)N_, (int)ncols, g, v1, (long)ld_s_, v2, (long)ld_s_), "axpy_sp gamma");
+        hemm_sp_calls_ += 2;
+        hemm_sp_vecs_ += 2 * ncols;
+    }
+    // the end of the call: the filtered (unlocked first-half) columns return to fp64; locked columns and the second half -
+    // which ApplyKconjugate rebuilds in fp64 right after - were never touched
+    void h2_end_single_precision()
+    {
+        if (sp_synced_)
+            hip_ok(chase_hip_convert_s2d(ctx_, CP, (int)N_, (int)(nevex_ - locked_), sV1_ + locked_ * ld_s_, (long)ld_s_,
+                                         dV1_ + locked_ * N_, (long)N_), "convert_s2d");
+        sp_active_ = false;
+        sp_synced_ = false;
+    }
     void lacpy(std::size_t ncols, const T* src, T* dst)
     {
         if (ncols) hip_ok(chase_hip_lacpy(ctx_, CP, (int)N_, (int)ncols, src, (long)N_, dst, (long)N_), "lacpy");
@@ -288,6 +379,9 @@ private:
     }
 
     T* dTmp_ = nullptr;                   // N x nc scratch: H V1 of the H^2 filter, deferred swaps, Lanczos scaling
+    bool h2_mixed_ = false;               // h2_mixed_precision
+    ST* sTmp_ = nullptr;                  // ld_s_ x nevex_: H V1 of an fp32 H^2 step
+    std::size_t sp_h_converts_ = 0;       // whole-matrix conversions of H into sH_
 };
 
 } // namespace chase_amd

@@ -36,6 +36,12 @@ struct HipImplExtras {
     virtual std::size_t hemm_sp_packed_calls() const { return 0; }  // the hemm_sp_split_calls that ran on the packed H
     virtual std::size_t sp_pack_full() const { return 0; }          // whole-matrix packs of H
     virtual std::size_t sp_pack_diag() const { return 0; }          // diagonal refreshes of the pack
+    // h2_mixed_precision (the single-GPU pseudo-Hermitian Impl): an H^2 filter call that starts while the smallest residual of the
+    // unlocked wanted pairs is above 1e-3 runs its products in fp32.  A key of its own: mixed_precision stays the Hermitian
+    // solvers'.  false = this Impl has no fp32 H^2 filter and `on` was not taken
+    virtual bool set_h2_mixed_precision(bool on) { return !on; }
+    virtual bool h2_mixed_precision() const { return false; }
+    virtual std::size_t sp_h_converts() const { return 0; }         // whole-matrix fp64 -> fp32 conversions of H (that Impl)
     virtual void set_device_rng(bool) = 0;
     virtual void reset_counters() = 0;
     virtual void* device_V1() = 0;               // current (local) vector block, pending swaps applied
@@ -93,6 +99,13 @@ inline void sp_prepack_env_ignored(const char* impl)
     static std::atomic<bool> said{false};
     if (sp_prepack_env() == 0 || said.exchange(true)) return;
     std::fprintf(stderr, "chase_hip: CHASE_HIP_SP_PREPACK is ignored by %s (single-GPU Hermitian solver only)\n", impl);
+}
+
+// CHASE_HIP_H2_MIXED_PRECISION=1: the construction-time default of h2_mixed_precision
+inline int h2_mixed_precision_env()
+{
+    const char* e = std::getenv("CHASE_HIP_H2_MIXED_PRECISION");
+    return e && std::atoi(e) != 0 ? 1 : 0;
 }
 
 } // namespace chase_amd

@@ -222,6 +222,14 @@ int chase_hip_solver_set(chase_hip_solver* s, const char* key, double v)
                 rc = chase_hip::set_error(CHASE_HIP_EINVAL, "solver_set: sp_prepack = 1 exists on the single-GPU Hermitian solver only "
                                                             "(the grid and the pseudo-Hermitian solvers do not pack H)");
         }
+        else if (name == "h2_mixed_precision") {
+            if (v != 0.0 && v != 1.0)
+                rc = chase_hip::set_error(CHASE_HIP_EINVAL, "solver_set: h2_mixed_precision is 0 or 1");
+            else if (!s->ex->set_h2_mixed_precision(v != 0))
+                rc = chase_hip::set_error(CHASE_HIP_EINVAL, "solver_set: h2_mixed_precision = 1 exists on the single-GPU pseudo-Hermitian "
+                                                            "solver only (the Hermitian solvers have mixed_precision, the grid "
+                                                            "pseudo-Hermitian solver filters in fp64)");
+        }
         else if (name == "reset_counters") s->ex->reset_counters();
         else rc = chase_hip::set_error(CHASE_HIP_EINVAL, "solver_set: unknown key");
     }); });
@@ -268,6 +276,8 @@ int chase_hip_solver_get(chase_hip_solver* s, const char* key, double* out)
         else if (name == "hemm_sp_packed_calls") *out = (double)s->ex->hemm_sp_packed_calls();
         else if (name == "sp_pack_full") *out = (double)s->ex->sp_pack_full();
         else if (name == "sp_pack_diag") *out = (double)s->ex->sp_pack_diag();
+        else if (name == "h2_mixed_precision") *out = s->ex->h2_mixed_precision() ? 1.0 : 0.0;
+        else if (name == "sp_h_converts") *out = (double)s->ex->sp_h_converts();
         else if (name == "resd_rechecked") *out = (double)s->ex->resd_rechecked();
         else if (name == "tape_qr_mismatches") *out = (double)s->tape.qr_variant_mismatches;   // of the last replay
         else if (name == "tape_qr_retries") *out = (double)s->ex->forced_qr_retries();   // shifted re-factorisations, replay
@@ -417,6 +427,13 @@ int chase_hip_op_shift(chase_hip_solver* s, double c, int isunshift)
         if (s->cplx) s->z->Shift(std::complex<double>(c, 0), isunshift != 0);
         else s->d->Shift(c, isunshift != 0);
     });
+}
+/* the bracket the drivers put around a filter call (FilterPhaseStart / FilterPhaseEnd): timing, and where the pseudo-Hermitian
+ * Impl decides on h2_mixed_precision */
+int chase_hip_op_filter_phase(chase_hip_solver* s, int start)
+{
+    if (!s) return chase_hip::set_error(CHASE_HIP_EINVAL, "filter_phase: NULL solver");
+    return guarded("FilterPhase", [&] { DISPATCH(s, { if (start) k.FilterPhaseStart(); else k.FilterPhaseEnd(); }); });
 }
 int chase_hip_op_hemm(chase_hip_solver* s, size_t block, const double* alpha, const double* beta, size_t offset_left,
                       size_t offset_right)

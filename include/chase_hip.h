@@ -303,6 +303,10 @@ int chase_hip_lacpy(chase_hip_ctx* ctx, int cplx, int m, int n, const void* A, l
 int chase_hip_convert_d2s(chase_hip_ctx* ctx, int cplx, int m, int n, const void* src, long ld_src, void* dst, long ld_dst);
 int chase_hip_convert_s2d(chase_hip_ctx* ctx, int cplx, int m, int n, const void* src, long ld_src, void* dst, long ld_dst);
 int chase_hip_diag_d2s(chase_hip_ctx* ctx, int cplx, int n, const void* H, long ldh, void* Hs, long ldhs);
+/* Y_j += gamma X_j on m x n fp32 (cplx: complex fp32) columns, leading dimensions in elements: the gamma term of the
+ * single-precision H^2 filter step.  gamma: 1 float (2 when cplx) on the HOST, handed to the kernel by value - no device-side
+ * scalar, no copy.  Rows >= m of a column are neither read nor written; m == 0 or n == 0 does nothing.  X and Y must not overlap */
+int chase_hip_axpy_sp(chase_hip_ctx* ctx, int cplx, int m, int n, const float* gamma, const void* X, long ldx, void* Y, long ldy);
 /* the list form of diag_d2s: Hs[rows[i], cols[i]] = (fp32) H[rows[i], cols[i]] for i < cnt, nothing else of Hs is touched; rows
  * and cols are DEVICE int arrays (the lists chase_hip_shift_list takes: the global diagonal inside a rank's block) */
 int chase_hip_diag_list_d2s(chase_hip_ctx* ctx, int cplx, const void* H, long ldh, void* Hs, long ldhs, const int* rows_dev,

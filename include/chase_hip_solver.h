@@ -78,7 +78,16 @@ int chase_hip_solver_destroy(chase_hip_solver* s);
  * chase_hip_gemm_*_bf16x3p - the bits of sp_product = 1 without it.  The first such call after H changed packs the whole
  * matrix, later ones refresh the diagonal (chase_hip_bf16x3_pack_diag).  In every other filter call the key is inert.  get
  * additionally: hemm_sp_packed_calls (the hemm_sp_split_calls that ran on the packed H), sp_pack_full (whole-matrix packs),
- * sp_pack_diag (diagonal refreshes); cleared by reset_counters. */
+ * sp_pack_diag (diagonal refreshes); cleared by reset_counters.
+ * h2_mixed_precision (set and get, 0 | 1 - anything else CHASE_HIP_EINVAL; default 0 or CHASE_HIP_H2_MIXED_PRECISION=1 at
+ * construction; the single-GPU pseudo-Hermitian solver only - 1 on a Hermitian solver or on the grid pseudo-Hermitian solver
+ * returns CHASE_HIP_EINVAL; a key of its own because the reference's CHASE_ENABLE_MIXED_PRECISION does nothing for
+ * pseudo-Hermitian matrices - mixed_precision and its environment variable leave those solves alone): the 1e-3 rule above, taken
+ * at FilterPhaseStart, puts an H^2 filter call into fp32 - V2 = alpha H (H V1) + beta V2 + gamma V1 as two fp32 MFMA products and
+ * chase_hip_axpy_sp on shadows of H and of the unlocked first-half columns; locked columns and the second half are never
+ * touched.  H^2 carries its shift in gamma, so the shadow of H is converted once per resident matrix.  Counted in hemm_sp_calls
+ * (two per step), hemm_sp_vecs, sp_filters; get additionally: sp_h_converts (whole-matrix conversions of H; cleared by
+ * reset_counters). */
 int chase_hip_solver_set(chase_hip_solver* s, const char* key, double value);
 int chase_hip_solver_get(chase_hip_solver* s, const char* key, double* value);
 int chase_hip_solver_solve(chase_hip_solver* s, int record_trace);
@@ -126,6 +135,9 @@ int chase_hip_op_initvecs(chase_hip_solver* s, int random);
 /* optional hook ReinitColumns (algorithm/interface.hpp; chase_cpu.hpp:329-349, pchase_cpu.hpp:313-331) */
 int chase_hip_op_reinit_columns(chase_hip_solver* s, size_t fixednev, const size_t* col_indices, size_t n_indices);
 int chase_hip_op_shift(chase_hip_solver* s, double c, int isunshift);
+/* FilterPhaseStart (start != 0) / FilterPhaseEnd (start == 0): the bracket the drivers put around a filter call - the device
+ * timer behind filter_ms, and where the pseudo-Hermitian Impl decides on h2_mixed_precision and widens the result.  Every solver */
+int chase_hip_op_filter_phase(chase_hip_solver* s, int start);
 int chase_hip_op_hemm(chase_hip_solver* s, size_t block, const double* alpha, const double* beta, size_t offset_left,
                       size_t offset_right);
 int chase_hip_op_hemm_h2(chase_hip_solver* s, size_t block, const double* alpha, const double* beta, const double* gamma,
