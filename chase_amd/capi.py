@@ -402,6 +402,15 @@ _sig("chase_hip_sqrt_inplace", c_int, c_void_p, c_void_p, c_int)
 _sig("chase_hip_fill_normal_bc", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_long, c_int, c_int, c_int,
      C.c_ulonglong)
 _sig("chase_hip_rows_indexed", c_int, c_void_p, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_int)
+# kernels of the single-precision solver
+_sig("chase_hip_shift_diag_sp", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_double)
+_sig("chase_hip_resid_norms_sp", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p)
+_sig("chase_hip_lacpy_sp", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_swap_cols_sp", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_long, c_long)
+_sig("chase_hip_permute_cols_sp", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_long, P(c_int), P(c_int), c_int)
+_sig("chase_hip_upload_matrix_sp", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_download_matrix_sp", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_complete_hermitian_sp", c_int, c_void_p, c_int, c_char, c_int, c_void_p, c_long)
 _sig("chase_hip_pack_upper", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p)
 _sig("chase_hip_unpack_upper", c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_long, c_int)
 
@@ -682,6 +691,44 @@ class Solver:
 
     def symOrHermMatrix(self, uplo):
         check(lib.chase_hip_op_sym_or_herm(self.h, uplo.encode()[0:1]), "symOrHermMatrix")
+
+
+_sig("chase_hip_solver_create_sp", c_int, P(c_void_p), c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_void_p, c_size_t,
+     c_void_p, c_size_t, c_void_p, c_int)
+
+
+class SpSolver(Solver):
+    """ChaseHipSp<T>: the single-precision Hermitian solver.  H32 (float32 / complex64, Fortran order) and V stay fp32 on the
+    device from start to end; ritzv, residuals and every driver scalar are fp64.  Starts with the reference's float defaults (tol
+    1e-5, deg 10, maxdeg 18, lanczositer 12).  h_on_device_ptr with N, cplx and ldh: the fp32 matrix already lives in HBM and is
+    used in place.  peek_v() returns the block widened to fp64."""
+
+    def __init__(self, ctx, H32, nev, nex, V=None, h_on_device_ptr=None, N=None, cplx=None, ldh=None):
+        self.ctx = ctx
+        if h_on_device_ptr is None:
+            assert H32.flags.f_contiguous and H32.ndim == 2 and H32.shape[0] == H32.shape[1]
+            assert H32.dtype in (np.float32, np.complex64), "SpSolver takes an fp32 matrix: round it yourself"
+            self.cplx = H32.dtype == np.complex64
+            self.N = H32.shape[0]
+            self.H = H32
+            hptr, on_dev, ldh = H32.ctypes.data, 0, self.N
+        else:
+            self.cplx, self.N, self.H = bool(cplx), int(N), None
+            hptr, on_dev, ldh = h_on_device_ptr, 1, int(ldh or N)
+        self.nev, self.nex = nev, nex
+        dt = np.complex64 if self.cplx else np.float32
+        self.V = np.zeros((self.N, nev + nex), dtype=dt, order="F") if V is None else V
+        assert self.V.flags.f_contiguous and self.V.dtype == dt
+        self.ritzv = np.zeros(nev + nex, dtype=np.float64)
+        h = c_void_p()
+        check(lib.chase_hip_solver_create_sp(C.byref(h), ctx.h, int(self.cplx), self.N, nev, nex, hptr, ldh,
+                                             self.V.ctypes.data, self.N, self.ritzv.ctypes.data, on_dev), "solver_create_sp")
+        self.h = h
+
+    def peek_v(self):
+        out = np.empty((self.N, self.nev + self.nex), dtype=np.complex128 if self.cplx else np.float64, order="F")
+        check(lib.chase_hip_solver_peek_v(self.h, self.ctx.h, out.ctypes.data, self.N), "peek_v")
+        return out
 
 
 _sig("chase_hip_solver_create_pseudo", c_int, P(c_void_p), c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_void_p,

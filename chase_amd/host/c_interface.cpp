@@ -1,5 +1,5 @@
 // c_interface.cpp — ChASE's application-facing C interface (interface/chase_c_interface.h:13-58,177-181; sequential fp64
-// entry points) on top of the HIP Impl.  Behaviour follows interface/chase_c_interface.cpp: one solver object per type
+// entry points, and the s / c ones on the single-precision solver) on top of the HIP Impl.  Behaviour follows interface/chase_c_interface.cpp: one solver object per type
 // kept between init / solve / finalize; zchase_ dispatches to the pseudo-Hermitian solver when that is the one that was
 // initialised (chase_c_interface.cpp:2204-2220); the *_internal_ inits own the vector / Ritz-value storage and
 // ?chase_get_eigenpairs_ copies the first nev eigenvectors and Ritz values out (chase_c_interface.cpp:2329-2400).
@@ -32,6 +32,25 @@ struct Slot {
 };
 Slot g_d, g_z, g_zp;
 int g_sym_check = 1;
+
+// single precision (schase_ / cchase_): H, V and the caller's ritzv are fp32; the solver's Ritz values are doubles kept here and
+// converted at the boundary after every solve
+struct SlotSp {
+    chase_hip_solver* s = nullptr;
+    int cplx = 0;
+    std::size_t N = 0, nev = 0, nex = 0;
+    void* V = nullptr;
+    float* ritzv32 = nullptr;                // the caller's (or own) fp32 Ritz values
+    std::vector<double> ritzv;               // what the solver writes
+    std::vector<float> own_v, own_ritzv;     // storage of the *_internal_ variants
+    void clear()
+    {
+        if (s) { chase_hip_solver_destroy(s); s = nullptr; }
+        own_v.clear(); own_v.shrink_to_fit(); own_ritzv.clear(); ritzv.clear();
+        V = nullptr; ritzv32 = nullptr;
+    }
+};
+SlotSp g_s, g_c;
 
 bool ensure_ctx()
 {
@@ -78,9 +97,90 @@ void get_pairs(const Slot& sl, void* out, int ld, double* ritzv)
         std::memcpy((char*)out + j * (std::size_t)ld * es, (const char*)sl.V + j * sl.N * es, sl.N * es);
     if (ritzv) std::memcpy(ritzv, sl.ritzv, sl.nev * sizeof(double));
 }
+void init_sp(SlotSp& sl, int cplx, int N, int nev, int nex, void* H, int ldh, void* V, float* ritzv, int* init)
+{
+    *init = 0;
+    if (!ensure_ctx() || N <= 0 || nev < 0 || nex < 0) return;
+    sl.clear();
+    const std::size_t ncol = (std::size_t)(nev + nex);
+    if (!V) {                                 // *_internal_: the interface owns V and ritzv
+        sl.own_v.assign((std::size_t)N * ncol * (cplx ? 2 : 1), 0.0f);
+        sl.own_ritzv.assign(ncol, 0.0f);
+        V = sl.own_v.data(); ritzv = sl.own_ritzv.data();
+    }
+    sl.cplx = cplx; sl.N = (std::size_t)N; sl.nev = (std::size_t)nev; sl.nex = (std::size_t)nex;
+    sl.V = V; sl.ritzv32 = ritzv;
+    sl.ritzv.assign(ncol, 0.0);
+    if (chase_hip_solver_create_sp(&sl.s, g_ctx, cplx, (size_t)N, (size_t)nev, (size_t)nex, H, (size_t)ldh, V, (size_t)N,
+                                   sl.ritzv.data(), 0) == 0)
+        *init = 1;
+}
+void solve_sp(SlotSp& sl, int deg, float tol, char mode, char opt, char qr)
+{
+    if (!sl.s) return;
+    chase_hip_solver_set(sl.s, "tol", (double)tol);
+    chase_hip_solver_set(sl.s, "deg", (double)deg);
+    chase_hip_solver_set(sl.s, "opt", opt == 'S' ? 1.0 : 0.0);
+    chase_hip_solver_set(sl.s, "approx", mode == 'A' ? 1.0 : 0.0);
+    chase_hip_solver_set(sl.s, "cholqr", qr == 'C' ? 1.0 : 0.0);
+    chase_hip_solver_solve(sl.s, 0);
+    if (sl.ritzv32)
+        for (std::size_t i = 0; i < sl.ritzv.size(); ++i) sl.ritzv32[i] = (float)sl.ritzv[i];
+}
+void get_pairs_sp(const SlotSp& sl, void* out, int ld, float* ritzv)
+{
+    if (!sl.s || !sl.V || !out || ld < (int)sl.N) return;
+    const std::size_t es = sl.cplx ? 8 : 4;
+    for (std::size_t j = 0; j < sl.nev; ++j)
+        std::memcpy((char*)out + j * (std::size_t)ld * es, (const char*)sl.V + j * sl.N * es, sl.N * es);
+    if (ritzv)
+        for (std::size_t i = 0; i < sl.nev; ++i) ritzv[i] = (float)sl.ritzv[i];
+}
 } // namespace
 
 extern "C" {
+/* ---- single precision (interface/chase_c_interface.h:19-41,178-212) ---- */
+void schase_init_(int* N, int* nev, int* nex, float* H, int* ldh, float* V, float* ritzv, int* init)
+{
+    init_sp(g_s, 0, *N, *nev, *nex, H, *ldh, V, ritzv, init);
+}
+void schase_init_internal_(int* N, int* nev, int* nex, float* H, int* ldh, int* init)
+{
+    init_sp(g_s, 0, *N, *nev, *nex, H, *ldh, nullptr, nullptr, init);
+}
+void schase_(int* deg, float* tol, char* mode, char* opt, char* qr) { solve_sp(g_s, *deg, *tol, *mode, *opt, *qr); }
+void schase_get_eigenpairs_(float* LEigsV, int* ld, float* ritzv) { if (ld) get_pairs_sp(g_s, LEigsV, *ld, ritzv); }
+void schase_finalize_(int* flag)
+{
+    g_s.clear();
+    if (flag) *flag = 0;
+}
+void cchase_init_(int* N, int* nev, int* nex, void* H, int* ldh, void* V, float* ritzv, int* init)
+{
+    init_sp(g_c, 1, *N, *nev, *nex, H, *ldh, V, ritzv, init);
+}
+void cchase_init_internal_(int* N, int* nev, int* nex, void* H, int* ldh, int* init)
+{
+    init_sp(g_c, 1, *N, *nev, *nex, H, *ldh, nullptr, nullptr, init);
+}
+void cchase_(int* deg, float* tol, char* mode, char* opt, char* qr) { solve_sp(g_c, *deg, *tol, *mode, *opt, *qr); }
+void cchase_get_eigenpairs_(void* LEigsV, int* ld, float* ritzv) { if (ld) get_pairs_sp(g_c, LEigsV, *ld, ritzv); }
+void cchase_finalize_(int* flag)
+{
+    g_c.clear();
+    if (flag) *flag = 0;
+}
+/* the reference forwards these to p[sc]chase_readHam_, which read into the live DISTRIBUTED solver; there is no single-precision
+ * grid solver here, hence nothing to read into */
+void schase_readHam_(const char* filename)
+{
+    std::fprintf(stderr, "chase_hip: schase_readHam_(%s): no single-precision distributed solver is live\n", filename ? filename : "");
+}
+void cchase_readHam_(const char* filename)
+{
+    std::fprintf(stderr, "chase_hip: cchase_readHam_(%s): no single-precision distributed solver is live\n", filename ? filename : "");
+}
+
 void dchase_init_(int* N, int* nev, int* nex, double* H, int* ldh, double* V, double* ritzv, int* init)
 {
     init_common(g_d, 0, 0, *N, *nev, *nex, H, *ldh, V, ritzv, init);
@@ -141,10 +241,13 @@ void chase_enable_sym_check_(int* flag) { if (flag) g_sym_check = *flag != 0; }
  * and return silently when none is.  tol / deg / opt / approx / cholqr are also arguments of ?chase_ / p?chase_, which set
  * them again at every solve (chase_c_interface.cpp:444-466,1873-1886); the others persist across solves. */
 chase_hip_solver* chase_hip_cshim_dist_solver(int cplx);
-chase_hip_solver* chase_hip_cshim_seq_solver(int kind) { return kind == 0 ? g_d.s : kind == 1 ? g_z.s : kind == 2 ? g_zp.s : nullptr; }
+chase_hip_solver* chase_hip_cshim_seq_solver(int kind)
+{
+    return kind == 0 ? g_d.s : kind == 1 ? g_z.s : kind == 2 ? g_zp.s : kind == 3 ? g_s.s : kind == 4 ? g_c.s : nullptr;
+}
 static void set_all(const char* key, double v)
 {
-    chase_hip_solver* live[5] = {g_d.s, g_z.s, g_zp.s, chase_hip_cshim_dist_solver(0), chase_hip_cshim_dist_solver(1)};
+    chase_hip_solver* live[7] = {g_d.s, g_z.s, g_zp.s, chase_hip_cshim_dist_solver(0), chase_hip_cshim_dist_solver(1), g_s.s, g_c.s};
     for (chase_hip_solver* s : live)
         if (s) chase_hip_solver_set(s, key, v);
 }

@@ -112,6 +112,7 @@ public:
     T* device_V2() { return dV2_; }
     T* device_H() { return dH_; }
     double filter_ms() const override { return filter_ms_; }
+    std::size_t device_bytes() const override { return device_bytes_; }
 
     // randomized Hermiticity check: ||H v - H^H v|| small  (reference: cpu::checkSymmetryEasy, symOrHerm.hpp)
     bool checkSymmetryEasy() override
@@ -488,6 +489,7 @@ protected:
         int rc = chase_hip_malloc(ctx_, p, bytes);
         if (rc) throw HipStatusError(rc, "chase_hip_malloc");
         owned_.push_back(*p);
+        device_bytes_ += bytes;
     }
     void upload_H()
     {
@@ -720,6 +722,7 @@ protected:
     double hv_shift_ = 0.0;
     void* dScal_ = nullptr;
     std::vector<void*> owned_;
+    std::size_t device_bytes_ = 0;         // what alloc() handed out (the Lanczos workspace is transient and not in it)
     double filter_ms_ = 0;
     std::size_t hemm_calls_ = 0, resd_rechecked_ = 0;
     long forced_recheck_ = -1;            // set_forced_recheck (single-rank replay)

@@ -42,6 +42,7 @@ struct HipImplExtras {
     virtual bool set_h2_mixed_precision(bool on) { return !on; }
     virtual bool h2_mixed_precision() const { return false; }
     virtual std::size_t sp_h_converts() const { return 0; }         // whole-matrix fp64 -> fp32 conversions of H (that Impl)
+    virtual std::size_t device_bytes() const { return 0; }          // sum of the Impl's own device allocations (single-GPU Impls)
     virtual void set_device_rng(bool) = 0;
     virtual void reset_counters() = 0;
     virtual void* device_V1() = 0;               // current (local) vector block, pending swaps applied

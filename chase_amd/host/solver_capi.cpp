@@ -12,6 +12,7 @@
 #include "chase_hip_impl.hpp"
 #include "pchase_hip_impl.hpp"
 #include "chase_hip_pseudo_impl.hpp"
+#include "chase_hip_sp_impl.hpp"
 #include "pchase_hip_pseudo_impl.hpp"
 #include "tape.hpp"
 
@@ -26,6 +27,9 @@ struct chase_hip_solver {
     HipImplExtras* ex = nullptr;                    // same object, Impl-specific extras
     pChaseHip<double>* pd = nullptr;                // set for the distributed Impl only
     pChaseHip<zc>* pz = nullptr;
+    ChaseHipSp<double>* sd = nullptr;               // set for the single-precision Impl only: its blocks are fp32
+    ChaseHipSp<zc>* sz = nullptr;
+    bool sp() const { return sd || sz; }
     SolveStats stats;
     CallTrace trace;
     std::string trace_text;
@@ -71,6 +75,30 @@ int chase_hip_solver_create(chase_hip_solver** out, chase_hip_ctx* ctx, int cplx
         } else {
             auto* p = new ChaseHip<double>(ctx, N, nev, nex, (double*)H, ldh, (double*)V, ldv, ritzv, h_on_device != 0);
             s->d.reset(p); s->ex = p;
+        }
+    });
+    if (rc) return rc;
+    *out = s.release();
+    return 0;
+}
+
+/* single-precision Hermitian Impl: H and V are fp32 / complex fp32, ritzv stays fp64; the reference's float defaults */
+int chase_hip_solver_create_sp(chase_hip_solver** out, chase_hip_ctx* ctx, int cplx, size_t N, size_t nev, size_t nex,
+                               const void* H32, size_t ldh, void* V32, size_t ldv, double* ritzv, int h_on_device)
+{
+    if (!out || !ctx || !H32 || !V32 || !ritzv) return chase_hip::set_error(CHASE_HIP_EINVAL, "solver_create_sp: NULL argument");
+    auto s = std::make_unique<chase_hip_solver>();
+    s->cplx = cplx ? 1 : 0;
+    chase_hip_host_lapack_warmup();          // not fatal here: a missing provider is reported by the first LAPACK call
+    using cf = std::complex<float>;
+    int rc = guarded("solver_create_sp", [&] {
+        if (cplx) {
+            auto* p = new ChaseHipSp<zc>(ctx, N, nev, nex, (cf*)const_cast<void*>(H32), ldh, (cf*)V32, ldv, ritzv, h_on_device != 0);
+            s->z.reset(p); s->ex = p; s->sz = p;
+        } else {
+            auto* p = new ChaseHipSp<double>(ctx, N, nev, nex, (float*)const_cast<void*>(H32), ldh, (float*)V32, ldv, ritzv,
+                                             h_on_device != 0);
+            s->d.reset(p); s->ex = p; s->sd = p;
         }
     });
     if (rc) return rc;
@@ -184,6 +212,10 @@ int chase_hip_solver_set(chase_hip_solver* s, const char* key, double v)
     if (!s || !key) return chase_hip::set_error(CHASE_HIP_EINVAL, "solver_set: NULL argument");
     const std::string name(key);
     int rc = 0;
+    if (s->sp() && v != 0.0 &&
+        (name == "mixed_precision" || name == "sp_product" || name == "sp_prepack" || name == "h2_mixed_precision"))
+        return chase_hip::set_error(CHASE_HIP_EINVAL, ("solver_set: " + name + " = 1 does not exist on the single-precision solver "
+                                                       "(every product of it is the fp32 MFMA one)").c_str());
     const int grc = guarded("solver_set", [&] { DISPATCH(s, {
         auto& c = k.GetConfig();
         if (name == "tol") c.SetTol(v);
@@ -278,6 +310,10 @@ int chase_hip_solver_get(chase_hip_solver* s, const char* key, double* out)
         else if (name == "sp_pack_diag") *out = (double)s->ex->sp_pack_diag();
         else if (name == "h2_mixed_precision") *out = s->ex->h2_mixed_precision() ? 1.0 : 0.0;
         else if (name == "sp_h_converts") *out = (double)s->ex->sp_h_converts();
+        else if (name == "device_bytes") {
+            if (s->pd || s->pz) rc = chase_hip::set_error(CHASE_HIP_EINVAL, "solver_get: device_bytes exists on the single-GPU solvers only");
+            else *out = (double)s->ex->device_bytes();
+        }
         else if (name == "resd_rechecked") *out = (double)s->ex->resd_rechecked();
         else if (name == "tape_qr_mismatches") *out = (double)s->tape.qr_variant_mismatches;   // of the last replay
         else if (name == "tape_qr_retries") *out = (double)s->ex->forced_qr_retries();   // shifted re-factorisations, replay
@@ -302,6 +338,8 @@ int chase_hip_solver_set_iteration_hook(chase_hip_solver* s, chase_hip_iteration
 int chase_hip_solver_solve(chase_hip_solver* s, int record_trace)
 {
     if (!s) return chase_hip::set_error(CHASE_HIP_EINVAL, "solver_solve: NULL solver");
+    if (s->sp() && s->tape_mode)
+        return chase_hip::set_error(CHASE_HIP_EINVAL, "solver_solve: the single-precision solver has no tape modes");
     s->stats = SolveStats();
     s->trace.lines.clear();
     s->trace.enabled = record_trace != 0;
@@ -341,6 +379,8 @@ int chase_hip_solver_solve(chase_hip_solver* s, int record_trace)
 int chase_hip_solver_tape_mode(chase_hip_solver* s, int mode)
 {
     if (!s || mode < 0 || mode > 2) return chase_hip::set_error(CHASE_HIP_EINVAL, "tape_mode: 0, 1 or 2");
+    if (s->sp() && mode != 0)
+        return chase_hip::set_error(CHASE_HIP_EINVAL, "tape_mode: the single-precision solver has no tape modes");
     s->tape_mode = mode;
     return 0;
 }
@@ -506,6 +546,7 @@ int chase_hip_solver_recompute_residuals(chase_hip_solver* s, size_t ncols, cons
 int chase_hip_solver_hash_v(chase_hip_solver* s, chase_hip_ctx* ctx, size_t ncols, unsigned long long* hash)
 {
     if (!s || !ctx || !hash) return chase_hip::set_error(CHASE_HIP_EINVAL, "hash_v: NULL argument");
+    if (s->sp()) return chase_hip::set_error(CHASE_HIP_EINVAL, "hash_v: not on the single-precision solver (its block is fp32)");
     return guarded("hash_v", [&] {
         DISPATCH(s, {
             if (ncols > k.GetRitzvBlockSize()) throw std::invalid_argument("more columns than the Impl holds");
@@ -516,6 +557,9 @@ int chase_hip_solver_hash_v(chase_hip_solver* s, chase_hip_ctx* ctx, size_t ncol
 
 int chase_hip_solver_peek_v(chase_hip_solver* s, chase_hip_ctx* ctx, void* host, size_t ldh)
 {
+    if (!s || !ctx || !host) return chase_hip::set_error(CHASE_HIP_EINVAL, "peek_v: NULL argument");
+    if (s->sp())                               // the fp32 block widened to fp64: same layout as the other solvers give
+        return guarded("peek_v", [&] { if (s->sz) s->sz->peek_widened((zc*)host, ldh); else s->sd->peek_widened((double*)host, ldh); });
     return guarded("peek_v", [&] {
         DISPATCH(s, hip_ok(chase_hip_download_matrix(ctx, s->cplx, (int)s->ex->local_rows(), (int)k.GetRitzvBlockSize(),
                                                      s->ex->device_V1(), (long)s->ex->local_rows(), host, (long)ldh),

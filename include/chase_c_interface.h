@@ -12,7 +12,11 @@
  *   ?chase_get_eigenpairs_(LEigsV, ld, ritzv): first nev eigenvectors (N x nev, ld >= N) and Ritz values (:177-181)
  *   zchase_init_pseudo_[internal_] / zchase_pseudo_ : pseudo-Hermitian (Bethe-Salpeter) problems through chase::Solve_pseudo;
  *              V has 2*(nev+nex) columns, ritzv 2*(nev+nex) entries (:44-58); zchase_ solves whichever type was initialised
- * The GPU is chosen by CHASE_HIP_DEVICE (default 0).  Single precision is not provided (this backend is fp64).
+ * The GPU is chosen by CHASE_HIP_DEVICE (default 0).
+ *   schase_* / cchase_* : the same sequence in single precision (interface/chase_c_interface.h:19-41,178-212): H, V and ritzv
+ *              are float / float _Complex / float, tol is a float; served by the single-precision solver
+ *              (chase_hip_solver_create_sp), whose Ritz values are converted at this boundary.  The pseudo-Hermitian
+ *              cchase_*pseudo* names and the p[sc]chase grid names are not provided.
  *
  * Distributed entry points (interface/chase_c_interface.h:61-65,95-99,126-128,149,177-195): every p?chase_init* of the
  * reference takes an MPI_Comm* and builds the 2D grid from it.  libchase_hip.so exports the same entry points with the
@@ -42,6 +46,16 @@ void zchase_init_pseudo_internal_(int* N, int* nev, int* nex, void* H, int* ldh,
 void zchase_pseudo_(int* deg, double* tol, char* mode, char* opt, char* qr);
 void dchase_get_eigenpairs_(double* LEigsV, int* ld, double* ritzv);
 void zchase_get_eigenpairs_(void* LEigsV, int* ld, double* ritzv);
+void schase_init_(int* N, int* nev, int* nex, float* H, int* ldh, float* V, float* ritzv, int* init);
+void schase_init_internal_(int* N, int* nev, int* nex, float* H, int* ldh, int* init);
+void schase_(int* deg, float* tol, char* mode, char* opt, char* qr);
+void schase_finalize_(int* flag);
+void schase_get_eigenpairs_(float* LEigsV, int* ld, float* ritzv);
+void cchase_init_(int* N, int* nev, int* nex, void* H, int* ldh, void* V, float* ritzv, int* init);
+void cchase_init_internal_(int* N, int* nev, int* nex, void* H, int* ldh, int* init);
+void cchase_(int* deg, float* tol, char* mode, char* opt, char* qr);
+void cchase_finalize_(int* flag);
+void cchase_get_eigenpairs_(void* LEigsV, int* ld, float* ritzv);
 void chase_enable_sym_check_(int* flag);     /* interface/chase_c_interface.cpp:4055: flag kept for callers that set it */
 /* unified configuration setters and build queries (interface/chase_c_interface.h:207-238): act on the live solver instance
  * (sequential or distributed), silent when none is initialised */
@@ -66,6 +80,8 @@ void chase_has_mpi_(int* flag);           /* 1 when libchase_hip_mpi.so is loade
 void chase_print_config_(void);
 void dchase_readHam_(const char* filename);  /* aliases of p?chase_readHam_ */
 void zchase_readHam_(const char* filename);
+void schase_readHam_(const char* filename);  /* no single-precision grid solver to read into: says so on stderr */
+void cchase_readHam_(const char* filename);
 
 /* ---- distributed (one process per GPU) ---- */
 struct chase_hip_grid;
@@ -77,7 +93,7 @@ struct chase_hip_solver* chase_hip_cshim_dist_solver(int cplx); /* the live dist
  * thread per GPU) with a solver of its own; 0 (default): ONE solver per type in the process, replaced by the next init from
  * any thread - the reference's static members (interface/chase_c_interface.cpp:905-1290).  Returns the previous setting. */
 int chase_hip_cshim_thread_ranks(int on);
-struct chase_hip_solver* chase_hip_cshim_seq_solver(int kind); /* live sequential solver: 0 real, 1 complex, 2 complex pseudo-Hermitian */
+struct chase_hip_solver* chase_hip_cshim_seq_solver(int kind); /* live sequential solver: 0 real, 1 complex, 2 complex pseudo-Hermitian, 3 / 4 single-precision real / complex */
 void pdchase_init_hip_(int* N, int* nev, int* nex, int* m, int* n, double* H, int* ldh, double* V, double* ritzv,
                        struct chase_hip_grid* grid, int* init);
 void pdchase_init_internal_hip_(int* N, int* nev, int* nex, int* m, int* n, double* H, int* ldh,

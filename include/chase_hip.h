@@ -341,6 +341,27 @@ int chase_hip_resid_norms(chase_hip_ctx* ctx, int cplx, int m, int n, const void
 int chase_hip_resid_norms_dev(chase_hip_ctx* ctx, int cplx, int m, int n, const void* W, long ldw, const void* V, long ldv,
                               const double* lambda_host, double* out_dev, int squared);
 
+/* ---- kernels of the single-precision solver (chase_hip_solver_create_sp); cplx = 0 (fp32) or 1 (complex fp32), leading
+ * dimensions in elements.  Each moves 16 bytes per access where base pointers and leading dimensions allow and element by element
+ * otherwise, and touches nothing outside its m x n window.  A negative extent, a leading dimension smaller than the row count, a
+ * negative column index or a NULL matrix of a non-empty operand is CHASE_HIP_EINVAL; empty extents return 0. -------------------- */
+/* H[i,i] = fl32(d0[i] + shift), i < n: the real part is the fp64 sum of the saved entry and the ACCUMULATED shift rounded once, the
+ * imaginary part of a complex entry is the saved one.  d0: n saved diagonal entries (device, element type of H).  In fp32
+ * (h + c) - c need not give h back, so the shifted diagonal is always formed from the saved one: shift == 0 restores it bit for bit */
+int chase_hip_shift_diag_sp(chase_hip_ctx* ctx, int cplx, int n, void* H, long ldh, const void* d0, double shift);
+/* resid[j] = || W_j - lambda_j V_j ||_2, j < n, on fp32 / complex fp32 columns: every entry is widened exactly, the differences are
+ * formed and their squares summed in fp64 (fixed order: bitwise reproducible).  lambda_host, resid_host: n doubles on the host */
+int chase_hip_resid_norms_sp(chase_hip_ctx* ctx, int cplx, int m, int n, const void* W, long ldw, const void* V, long ldv,
+                             const double* lambda_host, double* resid_host);
+/* the fp32 twins of lacpy, swap_cols, permute_cols, upload_matrix, download_matrix and complete_hermitian (same contracts) */
+int chase_hip_lacpy_sp(chase_hip_ctx* ctx, int cplx, int m, int n, const void* A, long lda, void* B, long ldb);
+int chase_hip_swap_cols_sp(chase_hip_ctx* ctx, int cplx, int m, void* V, long ldv, long i, long j);
+int chase_hip_permute_cols_sp(chase_hip_ctx* ctx, int cplx, int m, void* V, long ldv, void* scratch, long lds,
+                              const int* src_host, const int* dst_host, int cnt);
+int chase_hip_upload_matrix_sp(chase_hip_ctx* ctx, int cplx, int m, int n, const void* host, long ldh, void* dev, long ldd);
+int chase_hip_download_matrix_sp(chase_hip_ctx* ctx, int cplx, int m, int n, const void* dev, long ldd, void* host, long ldh);
+int chase_hip_complete_hermitian_sp(chase_hip_ctx* ctx, int cplx, char uplo, int n, void* A, long lda);
+
 /* ---- Cholesky-QR building blocks (replace cublasTsyherk / cusolverDnTpotrf / cublasTtrsm, cuda/cholqr.hpp:110-132) */
 int chase_hip_herk(chase_hip_ctx* ctx, int cplx, int n, int k, const void* V, long ldv, void* A, long lda);
 /* C (n x n) = A^H B for k x n operands whose product is Hermitian (Gram matrix: A = B; projected matrix of Rayleigh-Ritz:

@@ -33,6 +33,19 @@ int chase_hip_solver_create(chase_hip_solver** out, chase_hip_ctx* ctx, int cplx
  * runs chase::Solve_pseudo (algorithm/algorithm.inc:1834-2220). */
 int chase_hip_solver_create_pseudo(chase_hip_solver** out, chase_hip_ctx* ctx, int cplx, size_t N, size_t nev, size_t nex,
                                    void* H, size_t ldh, void* V, size_t ldv, double* ritzv, int h_on_device);
+/* Single-precision Hermitian Impl (ChaseHipSp, chase_amd/host/chase_hip_sp_impl.hpp; the reference's float / complex<float>
+ * instantiations): H32 (N x N, ldh) and V32 (N x (nev+nex), ldv) are fp32 (cplx: complex fp32) and stay fp32 on the device from
+ * start to end - no fp64 copy of H is ever made; ritzv, residuals and every scalar of the driver stay fp64 on the host.
+ * h_on_device != 0: H32 is a device pointer used in place at any ldh >= N.  The handle starts with the reference's single-precision
+ * defaults (algorithm/configuration.hpp:58-129): tol 1e-5, deg 10, maxdeg 18, lanczositer 12.  Residuals cannot go below about
+ * sqrt(N) 2^-24 ||H||: tol 1e-5 needs ||H|| of order 1.
+ * Filter products are chase_hip_gemm_s / _c, counted in hemm_sp_calls / hemm_sp_vecs (hemm_calls stays 0; sp_filters counts filter
+ * calls); QR runs in fp64 on the widened block with the thresholds 1e4 / 1e1; Rayleigh-Ritz projects into fp64.
+ * Every chase_hip_solver_* / chase_hip_op_* entry point works on the handle, except: the tape modes, chase_hip_solver_hash_v and
+ * device_rng = 1 return CHASE_HIP_EINVAL, and so does a 1 for any of the four precision switches of chase_hip_solver_set (see
+ * there; their environment variables are ignored).  chase_hip_solver_peek_v returns the block widened to fp64. */
+int chase_hip_solver_create_sp(chase_hip_solver** out, chase_hip_ctx* ctx, int cplx, size_t N, size_t nev, size_t nex,
+                               const void* H32, size_t ldh, void* V32, size_t ldv, double* ritzv, int h_on_device);
 /* Distributed Impl (pChASECPU / pChASEGPU constructor contract, pchase_cpu.hpp:92-93): H_loc is this rank's DEVICE
  * block of the N x N matrix, distributed block-cyclically with (mb, nb) over the grid (mb = nb = 0: the reference's block
  * layout); the nev+nex vectors live distributed on the devices (chase_hip_psolver_{upload,download}_v move a rank's
@@ -87,7 +100,11 @@ int chase_hip_solver_destroy(chase_hip_solver* s);
  * chase_hip_axpy_sp on shadows of H and of the unlocked first-half columns; locked columns and the second half are never
  * touched.  H^2 carries its shift in gamma, so the shadow of H is converted once per resident matrix.  Counted in hemm_sp_calls
  * (two per step), hemm_sp_vecs, sp_filters; get additionally: sp_h_converts (whole-matrix conversions of H; cleared by
- * reset_counters). */
+ * reset_counters).
+ * On a single-precision solver (chase_hip_solver_create_sp) a 1 for mixed_precision, sp_product, sp_prepack or h2_mixed_precision
+ * returns CHASE_HIP_EINVAL (0 is accepted), and CHASE_HIP_MIXED_PRECISION / _SP_PRODUCT / _SP_PREPACK are not read.
+ * device_bytes (get only; the single-GPU solvers - CHASE_HIP_EINVAL on a grid): the sum of the Impl's own device allocations (H
+ * unless it is the caller's, the vector blocks, scratch, shadows made so far; transient Lanczos workspace is not in it). */
 int chase_hip_solver_set(chase_hip_solver* s, const char* key, double value);
 int chase_hip_solver_get(chase_hip_solver* s, const char* key, double* value);
 int chase_hip_solver_solve(chase_hip_solver* s, int record_trace);
