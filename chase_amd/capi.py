@@ -293,6 +293,14 @@ class Context:
         """Y_j += gamma X_j on m x n fp32 / complex fp32 columns; device addresses, leading dimensions in elements."""
         check(lib.chase_hip_axpy_sp(self.h, int(cplx), m, n, _c2(gamma), X, ldx, Y, ldy), "axpy_sp")
 
+    def scale_rows_sp(self, m, n, X, ldx, row0, s, cplx):
+        """X[row0:m, :n] *= s on fp32 / complex fp32 columns (one fp32 multiply per component); device address, ld in elements."""
+        check(lib.chase_hip_scale_rows_sp(self.h, int(cplx), m, n, X, ldx, row0, float(s)), "scale_rows_sp")
+
+    def kconj_sp(self, N, n, first, ldf, second, lds, cplx):
+        """second = K-conjugate of first (n fp32 / complex fp32 columns of N rows): halves swapped, complex entries conjugated."""
+        check(lib.chase_hip_kconj_sp(self.h, int(cplx), N, n, first, ldf, second, lds), "kconj_sp")
+
     def to_single(self, dA):
         """fp32 / complex fp32 copy of an fp64 / complex fp64 DeviceArray, converted on the device."""
         cplx = dA.dtype == np.complex128
@@ -406,6 +414,8 @@ _sig("chase_hip_rows_indexed", c_int, c_void_p, c_int, c_void_p, c_long, c_void_
 _sig("chase_hip_shift_diag_sp", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_double)
 _sig("chase_hip_resid_norms_sp", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p)
 _sig("chase_hip_lacpy_sp", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_scale_rows_sp", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_int, C.c_float)
+_sig("chase_hip_kconj_sp", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
 _sig("chase_hip_swap_cols_sp", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_long, c_long)
 _sig("chase_hip_permute_cols_sp", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_long, P(c_int), P(c_int), c_int)
 _sig("chase_hip_upload_matrix_sp", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
@@ -789,4 +799,40 @@ class PseudoSolver(Solver):
         n = self.nev + self.nex - offset
         out = np.zeros(n)
         check(lib.chase_hip_op_resd(self.h, self.ritzv.ctypes.data + 8 * offset, out.ctypes.data, offset), "Resd")
+        return out
+
+
+_sig("chase_hip_solver_create_pseudo_sp", c_int, P(c_void_p), c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_void_p,
+     c_size_t, c_void_p, c_size_t, c_void_p, c_int)
+
+
+class SpPseudoSolver(PseudoSolver):
+    """ChaseHipSpPseudo<T>: the single-precision pseudo-Hermitian (BSE) solver.  H32 (float32 / complex64, Fortran order) and V
+    (N x 2*(nev+nex)) stay fp32 on the device from start to end; ritzv and resid() are fp64 of length 2*(nev+nex).  Starts with the
+    reference's float defaults.  h_on_device_ptr with N, cplx and ldh: the fp32 matrix already lives in HBM and is used in place.
+    peek_v() returns the block widened to fp64.  The op methods are PseudoSolver's."""
+
+    def __init__(self, ctx, H32, nev, nex, h_on_device_ptr=None, N=None, cplx=None, ldh=None):
+        self.ctx, self.H = ctx, H32
+        if h_on_device_ptr is None:
+            assert H32.flags.f_contiguous and H32.ndim == 2 and H32.shape[0] == H32.shape[1]
+            assert H32.dtype in (np.float32, np.complex64), "SpPseudoSolver takes an fp32 matrix: round it yourself"
+            self.cplx, self.N = H32.dtype == np.complex64, H32.shape[0]
+            hptr, on_dev, ldh = H32.ctypes.data, 0, self.N
+        else:
+            self.cplx, self.N = bool(cplx), int(N)
+            hptr, on_dev, ldh = h_on_device_ptr, 1, int(ldh or N)
+        self.nev, self.nex = nev, nex
+        self.ncol = 2 * (nev + nex)
+        self.V = np.zeros((self.N, self.ncol), dtype=np.complex64 if self.cplx else np.float32, order="F")
+        self.ritzv = np.zeros(self.ncol)
+        h = c_void_p()
+        check(lib.chase_hip_solver_create_pseudo_sp(C.byref(h), ctx.h, int(self.cplx), self.N, nev, nex, hptr, ldh,
+                                                    self.V.ctypes.data, self.N, self.ritzv.ctypes.data, on_dev),
+              "solver_create_pseudo_sp")
+        self.h = h
+
+    def peek_v(self):
+        out = np.empty((self.N, self.ncol), dtype=np.complex128 if self.cplx else np.float64, order="F")
+        check(lib.chase_hip_solver_peek_v(self.h, self.ctx.h, out.ctypes.data, self.N), "peek_v")
         return out

@@ -109,6 +109,11 @@ int convert_s2d(hipStream_t st, const float* src, long ld_src, double* dst, long
 int diag_d2s(hipStream_t st, const double* H, long ldh, float* Hs, long ldhs, int n, int ept);                  // Hs[i,i] = (float)H[i,i]
 // Y_j += (gr + i gi) X_j on fp32 columns of ms floats (m * ept), leading dimensions in floats; gamma by value
 int axpy_sp(hipStream_t st, bool cplx, float gr, float gi, const float* X, long ldx_f, float* Y, long ldy_f, long ms, int ncols);
+// sp_kernels.hip: X[i, j] *= s for the floats i >= row0_f of the mf floats of each column (one fp32 multiply per float)
+int scale_rows_sp(hipStream_t st, float* X, long ldx_f, long row0_f, long mf, int ncols, float s);
+// sp_kernels.hip: second[hf + i, j] = conj(first[i, j]), second[i, j] = conj(first[hf + i, j]), i < hf floats (hf = N/2 * ept);
+// cplx: the odd floats (imaginary parts) change sign, real: the plain half swap.  first and second must not overlap
+int kconj_sp(hipStream_t st, bool cplx, const float* first, long ldf_f, float* second, long lds_f, long hf, int ncols);
 // Hs[rows[i], cols[i]] = (float)H[rows[i], cols[i]], i < cnt (device lists: the diagonal inside a rank's block)
 int diag_list_d2s(hipStream_t st, const double* H, long ldh, float* Hs, long ldhs, const int* rows, const int* cols, int cnt, int ept);
 

@@ -8,9 +8,13 @@
 //                   s = 0 gives the saved bits back
 //   resid_norms_sp  || W_j - lambda_j V_j ||_2 of fp32 columns: every term widened exactly, formed and summed in fp64, wave64
 //                   shuffle reduction in a fixed order (bitwise reproducible)
+// and, for the single-precision pseudo-Hermitian solver (chase_hip_sp_pseudo_impl.hpp), both exact by construction:
+//   scale_rows_sp   X[row0:, :] *= s, one fp32 multiply per component (s = -1: the S flip, s = fl32(0.001): the start-vector damping)
+//   kconj_sp        second half of the block = K-conjugate of the first: the two half-column copies and the conjugation in one pass
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "ctx.h"
+#include "kernels.h"
 #include "../../include/chase_hip.h"
 
 using namespace chase_hip;
@@ -117,6 +121,46 @@ __global__ __launch_bounds__(256) void resid_norms_sp_kernel(const float* __rest
     if (threadIdx.x == 0) out[j] = sqrt((sm[0] + sm[1]) + (sm[2] + sm[3]));
 }
 
+// X[i, j] *= s over the len floats of each column that start at p0 (the caller's row0): one fp32 multiply per float
+__global__ __launch_bounds__(256) void scale_rows_sp_kernel(float* __restrict__ p0, long ldx_f, long len, int ncols, float s, int vec)
+{
+    for (int j = blockIdx.y; j < ncols; j += gridDim.y) {
+        float* p = p0 + (long)j * ldx_f;
+        const long n4 = vec ? (len >> 2) : 0;
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+            float4 v = ((float4*)p)[i];
+            v.x *= s; v.y *= s; v.z *= s; v.w *= s;
+            ((float4*)p)[i] = v;
+        }
+        for (long i = 4 * n4 + (long)blockIdx.x * 256 + threadIdx.x; i < len; i += (long)gridDim.x * 256) p[i] *= s;
+    }
+}
+
+// dst[hf + i] = conj(src[i]), dst[i] = conj(src[hf + i]) for the i < hf floats of each half column; CP: the odd floats are the
+// imaginary parts (hf is even then) and change sign
+template <bool CP>
+__global__ __launch_bounds__(256) void kconj_sp_kernel(const float* __restrict__ src, long ldf_f, float* __restrict__ dst, long lds_f,
+                                                       long hf, int ncols, int vec)
+{
+    for (int j = blockIdx.y; j < ncols; j += gridDim.y) {
+        const float* s = src + (long)j * ldf_f;
+        float* d = dst + (long)j * lds_f;
+        const long n4 = vec ? (hf >> 2) : 0;                 // vec: hf is a multiple of 4, both halves start on 16 bytes
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+            float4 a = ((const float4*)s)[i], b = ((const float4*)(s + hf))[i];
+            if (CP) { a.y = -a.y; a.w = -a.w; b.y = -b.y; b.w = -b.w; }
+            ((float4*)(d + hf))[i] = a;
+            ((float4*)d)[i] = b;
+        }
+        for (long i = 4 * n4 + (long)blockIdx.x * 256 + threadIdx.x; i < hf; i += (long)gridDim.x * 256) {
+            const float a = s[i], b = s[hf + i];
+            const bool im = CP && (i & 1);
+            d[hf + i] = im ? -a : a;
+            d[i] = im ? -b : b;
+        }
+    }
+}
+
 // Hermitian completion from the stored triangle: up != 0: A[i,j] = conj(A[j,i]) for i > j, else for i < j; the diagonal stays
 __global__ __launch_bounds__(256) void complete_hermitian_sp_kernel(float* __restrict__ A, long lda, int n, int ept, int up)
 {
@@ -140,7 +184,55 @@ inline int ept_of(int cplx) { return cplx ? 2 : 1; }
 
 } // namespace
 
+namespace chase_hip {
+
+int scale_rows_sp(hipStream_t st, float* X, long ldx_f, long row0_f, long mf, int ncols, float s)
+{
+    if (row0_f >= mf || ncols <= 0) return 0;
+    float* p0 = X + row0_f;
+    const int vec = (ldx_f & 3) == 0 && a16(p0);
+    hipLaunchKernelGGL(scale_rows_sp_kernel, grid2(mf - row0_f, ncols), dim3(256), 0, st, p0, ldx_f, mf - row0_f, ncols, s, vec);
+    return (int)hipGetLastError();
+}
+
+int kconj_sp(hipStream_t st, bool cplx, const float* first, long ldf_f, float* second, long lds_f, long hf, int ncols)
+{
+    if (hf <= 0 || ncols <= 0) return 0;
+    const int vec = (ldf_f & 3) == 0 && (lds_f & 3) == 0 && (hf & 3) == 0 && a16(first) && a16(second);
+    if (cplx) hipLaunchKernelGGL(kconj_sp_kernel<true>, grid2(hf, ncols), dim3(256), 0, st, first, ldf_f, second, lds_f, hf, ncols, vec);
+    else      hipLaunchKernelGGL(kconj_sp_kernel<false>, grid2(hf, ncols), dim3(256), 0, st, first, ldf_f, second, lds_f, hf, ncols, vec);
+    return (int)hipGetLastError();
+}
+
+} // namespace chase_hip
+
 extern "C" {
+
+int chase_hip_scale_rows_sp(chase_hip_ctx* c, int cplx, int m, int n, void* X, long ldx, int row0, float s)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "scale_rows_sp: NULL ctx");
+    (void)hipSetDevice(c->device);
+    if (c->oplog_on) c->oplog_add("scale_rows_sp", m, n, 0, 0);
+    if (m < 0 || n < 0 || ldx < m || row0 < 0 || row0 > m) return set_error(CHASE_HIP_EINVAL, "scale_rows_sp: bad shape");
+    if (m == 0 || n == 0 || row0 == m) return 0;
+    if (!X) return set_error(CHASE_HIP_EINVAL, "scale_rows_sp: NULL matrix");
+    const int e = ept_of(cplx);
+    HIPCHK((hipError_t)scale_rows_sp(c->stream, (float*)X, ldx * e, (long)row0 * e, (long)m * e, n, s));
+    return 0;
+}
+
+int chase_hip_kconj_sp(chase_hip_ctx* c, int cplx, int N, int n, const void* first, long ldf, void* second, long lds_)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "kconj_sp: NULL ctx");
+    (void)hipSetDevice(c->device);
+    if (c->oplog_on) c->oplog_add("kconj_sp", N, n, 0, 0);
+    if (N < 0 || (N & 1) || n < 0 || ldf < N || lds_ < N) return set_error(CHASE_HIP_EINVAL, "kconj_sp: bad shape (N even, ld >= N)");
+    if (N == 0 || n == 0) return 0;
+    if (!first || !second) return set_error(CHASE_HIP_EINVAL, "kconj_sp: NULL matrix");
+    const int e = ept_of(cplx);
+    HIPCHK((hipError_t)kconj_sp(c->stream, cplx != 0, (const float*)first, ldf * e, (float*)second, lds_ * e, (long)(N / 2) * e, n));
+    return 0;
+}
 
 int chase_hip_shift_diag_sp(chase_hip_ctx* c, int cplx, int n, void* H, long ldh, const void* d0, double shift)
 {

@@ -1,5 +1,5 @@
 // c_interface.cpp — ChASE's application-facing C interface (interface/chase_c_interface.h:13-58,177-181; sequential fp64
-// entry points, and the s / c ones on the single-precision solver) on top of the HIP Impl.  Behaviour follows interface/chase_c_interface.cpp: one solver object per type
+// entry points, and the s / c ones - cchase_*pseudo* included - on the single-precision solvers) on top of the HIP Impl.  Behaviour follows interface/chase_c_interface.cpp: one solver object per type
 // kept between init / solve / finalize; zchase_ dispatches to the pseudo-Hermitian solver when that is the one that was
 // initialised (chase_c_interface.cpp:2204-2220); the *_internal_ inits own the vector / Ritz-value storage and
 // ?chase_get_eigenpairs_ copies the first nev eigenvectors and Ritz values out (chase_c_interface.cpp:2329-2400).
@@ -37,7 +37,7 @@ int g_sym_check = 1;
 // converted at the boundary after every solve
 struct SlotSp {
     chase_hip_solver* s = nullptr;
-    int cplx = 0;
+    int cplx = 0, pseudo = 0;
     std::size_t N = 0, nev = 0, nex = 0;
     void* V = nullptr;
     float* ritzv32 = nullptr;                // the caller's (or own) fp32 Ritz values
@@ -50,7 +50,7 @@ struct SlotSp {
         V = nullptr; ritzv32 = nullptr;
     }
 };
-SlotSp g_s, g_c;
+SlotSp g_s, g_c, g_cp;        // g_cp: cchase_init_pseudo_ (2 (nev+nex) columns and Ritz values)
 
 bool ensure_ctx()
 {
@@ -97,23 +97,25 @@ void get_pairs(const Slot& sl, void* out, int ld, double* ritzv)
         std::memcpy((char*)out + j * (std::size_t)ld * es, (const char*)sl.V + j * sl.N * es, sl.N * es);
     if (ritzv) std::memcpy(ritzv, sl.ritzv, sl.nev * sizeof(double));
 }
-void init_sp(SlotSp& sl, int cplx, int N, int nev, int nex, void* H, int ldh, void* V, float* ritzv, int* init)
+void init_sp(SlotSp& sl, int cplx, int pseudo, int N, int nev, int nex, void* H, int ldh, void* V, float* ritzv, int* init)
 {
     *init = 0;
     if (!ensure_ctx() || N <= 0 || nev < 0 || nex < 0) return;
     sl.clear();
-    const std::size_t ncol = (std::size_t)(nev + nex);
+    const std::size_t ncol = (pseudo ? 2 : 1) * (std::size_t)(nev + nex);
     if (!V) {                                 // *_internal_: the interface owns V and ritzv
         sl.own_v.assign((std::size_t)N * ncol * (cplx ? 2 : 1), 0.0f);
         sl.own_ritzv.assign(ncol, 0.0f);
         V = sl.own_v.data(); ritzv = sl.own_ritzv.data();
     }
-    sl.cplx = cplx; sl.N = (std::size_t)N; sl.nev = (std::size_t)nev; sl.nex = (std::size_t)nex;
+    sl.cplx = cplx; sl.pseudo = pseudo; sl.N = (std::size_t)N; sl.nev = (std::size_t)nev; sl.nex = (std::size_t)nex;
     sl.V = V; sl.ritzv32 = ritzv;
     sl.ritzv.assign(ncol, 0.0);
-    if (chase_hip_solver_create_sp(&sl.s, g_ctx, cplx, (size_t)N, (size_t)nev, (size_t)nex, H, (size_t)ldh, V, (size_t)N,
-                                   sl.ritzv.data(), 0) == 0)
-        *init = 1;
+    const int rc = pseudo ? chase_hip_solver_create_pseudo_sp(&sl.s, g_ctx, cplx, (size_t)N, (size_t)nev, (size_t)nex, H, (size_t)ldh,
+                                                              V, (size_t)N, sl.ritzv.data(), 0)
+                          : chase_hip_solver_create_sp(&sl.s, g_ctx, cplx, (size_t)N, (size_t)nev, (size_t)nex, H, (size_t)ldh, V,
+                                                       (size_t)N, sl.ritzv.data(), 0);
+    if (rc == 0) *init = 1;
 }
 void solve_sp(SlotSp& sl, int deg, float tol, char mode, char opt, char qr)
 {
@@ -142,11 +144,11 @@ extern "C" {
 /* ---- single precision (interface/chase_c_interface.h:19-41,178-212) ---- */
 void schase_init_(int* N, int* nev, int* nex, float* H, int* ldh, float* V, float* ritzv, int* init)
 {
-    init_sp(g_s, 0, *N, *nev, *nex, H, *ldh, V, ritzv, init);
+    init_sp(g_s, 0, 0, *N, *nev, *nex, H, *ldh, V, ritzv, init);
 }
 void schase_init_internal_(int* N, int* nev, int* nex, float* H, int* ldh, int* init)
 {
-    init_sp(g_s, 0, *N, *nev, *nex, H, *ldh, nullptr, nullptr, init);
+    init_sp(g_s, 0, 0, *N, *nev, *nex, H, *ldh, nullptr, nullptr, init);
 }
 void schase_(int* deg, float* tol, char* mode, char* opt, char* qr) { solve_sp(g_s, *deg, *tol, *mode, *opt, *qr); }
 void schase_get_eigenpairs_(float* LEigsV, int* ld, float* ritzv) { if (ld) get_pairs_sp(g_s, LEigsV, *ld, ritzv); }
@@ -157,17 +159,40 @@ void schase_finalize_(int* flag)
 }
 void cchase_init_(int* N, int* nev, int* nex, void* H, int* ldh, void* V, float* ritzv, int* init)
 {
-    init_sp(g_c, 1, *N, *nev, *nex, H, *ldh, V, ritzv, init);
+    g_cp.clear();
+    init_sp(g_c, 1, 0, *N, *nev, *nex, H, *ldh, V, ritzv, init);
 }
 void cchase_init_internal_(int* N, int* nev, int* nex, void* H, int* ldh, int* init)
 {
-    init_sp(g_c, 1, *N, *nev, *nex, H, *ldh, nullptr, nullptr, init);
+    g_cp.clear();
+    init_sp(g_c, 1, 0, *N, *nev, *nex, H, *ldh, nullptr, nullptr, init);
 }
-void cchase_(int* deg, float* tol, char* mode, char* opt, char* qr) { solve_sp(g_c, *deg, *tol, *mode, *opt, *qr); }
-void cchase_get_eigenpairs_(void* LEigsV, int* ld, float* ritzv) { if (ld) get_pairs_sp(g_c, LEigsV, *ld, ritzv); }
-void cchase_finalize_(int* flag)
+/* single-precision pseudo-Hermitian (interface/chase_c_interface.h:46-57): V spans 2 (nev+nex) columns, ritzv 2 (nev+nex) floats */
+void cchase_init_pseudo_(int* N, int* nev, int* nex, void* H, int* ldh, void* V, float* ritzv, int* init)
 {
     g_c.clear();
+    init_sp(g_cp, 1, 1, *N, *nev, *nex, H, *ldh, V, ritzv, init);
+}
+void cchase_init_pseudo_internal_(int* N, int* nev, int* nex, void* H, int* ldh, int* init)
+{
+    g_c.clear();
+    init_sp(g_cp, 1, 1, *N, *nev, *nex, H, *ldh, nullptr, nullptr, init);
+}
+void cchase_pseudo_(int* deg, float* tol, char* mode, char* opt, char* qr) { solve_sp(g_cp, *deg, *tol, *mode, *opt, *qr); }
+void cchase_(int* deg, float* tol, char* mode, char* opt, char* qr)
+{
+    if (g_cp.s) solve_sp(g_cp, *deg, *tol, *mode, *opt, *qr);           // the type that was initialised decides
+    else solve_sp(g_c, *deg, *tol, *mode, *opt, *qr);
+}
+void cchase_get_eigenpairs_(void* LEigsV, int* ld, float* ritzv)
+{
+    if (!ld) return;
+    if (g_cp.s) get_pairs_sp(g_cp, LEigsV, *ld, ritzv);
+    else get_pairs_sp(g_c, LEigsV, *ld, ritzv);
+}
+void cchase_finalize_(int* flag)
+{
+    g_c.clear(); g_cp.clear();
     if (flag) *flag = 0;
 }
 /* the reference forwards these to p[sc]chase_readHam_, which read into the live DISTRIBUTED solver; there is no single-precision
@@ -243,11 +268,12 @@ void chase_enable_sym_check_(int* flag) { if (flag) g_sym_check = *flag != 0; }
 chase_hip_solver* chase_hip_cshim_dist_solver(int cplx);
 chase_hip_solver* chase_hip_cshim_seq_solver(int kind)
 {
-    return kind == 0 ? g_d.s : kind == 1 ? g_z.s : kind == 2 ? g_zp.s : kind == 3 ? g_s.s : kind == 4 ? g_c.s : nullptr;
+    return kind == 0 ? g_d.s : kind == 1 ? g_z.s : kind == 2 ? g_zp.s : kind == 3 ? g_s.s : kind == 4 ? g_c.s : kind == 5 ? g_cp.s : nullptr;
 }
 static void set_all(const char* key, double v)
 {
-    chase_hip_solver* live[7] = {g_d.s, g_z.s, g_zp.s, chase_hip_cshim_dist_solver(0), chase_hip_cshim_dist_solver(1), g_s.s, g_c.s};
+    chase_hip_solver* live[8] = {g_d.s, g_z.s, g_zp.s, chase_hip_cshim_dist_solver(0), chase_hip_cshim_dist_solver(1), g_s.s, g_c.s,
+                                 g_cp.s};
     for (chase_hip_solver* s : live)
         if (s) chase_hip_solver_set(s, key, v);
 }

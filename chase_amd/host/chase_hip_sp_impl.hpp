@@ -17,6 +17,8 @@
 //
 // It carries none of ChaseHip's fp64 shadows, cached H V, re-check or packing state.  Plugging it into a ChASE checkout as
 // ChaseBase<float> is out of scope.
+// ChaseHipSpPseudo (chase_hip_sp_pseudo_impl.hpp) derives from it as ChaseHipPseudo does from ChaseHip: the members are protected, the
+// vector blocks have nc_ columns (nev+nex here, twice that there), and QR's factorisation is qr_block with a hook on the widened block.
 #pragma once
 #include "chase_hip_impl.hpp"
 
@@ -31,13 +33,14 @@ public:
 
     // H: N x N fp32 column-major (ldh), V1: N x (nev+nex) fp32 (ldv), ritzv: nev+nex doubles.  h_on_device: H already lives in
     // HBM and is used in place at its ld (shifted and unshifted by the filter)
+    // ncols / a_elems: the pseudo-Hermitian Impl (chase_hip_sp_pseudo_impl.hpp) holds 2 (nev+nex) columns and two projected matrices
     ChaseHipSp(chase_hip_ctx* ctx, std::size_t N, std::size_t nev, std::size_t nex, ST* H, std::size_t ldh, ST* V1,
-               std::size_t ldv, R* ritzv, bool h_on_device = false)
-        : ctx_(ctx), N_(N), nev_(nev), nex_(nex), nevex_(nev + nex), H_(H), ldh_(ldh), V1_(V1), ldv_(ldv), ritzv_(ritzv),
-          h_on_device_(h_on_device), config_(N, nev, nex), resid_(nevex_, 0), perm_(nevex_)
+               std::size_t ldv, R* ritzv, bool h_on_device = false, std::size_t ncols = 0, std::size_t a_elems = 0)
+        : ctx_(ctx), N_(N), nev_(nev), nex_(nex), nevex_(nev + nex), nc_(ncols ? ncols : nev + nex), H_(H), ldh_(ldh), V1_(V1),
+          ldv_(ldv), ritzv_(ritzv), h_on_device_(h_on_device), config_(N, nev, nex), resid_(nc_, 0), perm_(nc_)
     {
         if (!ctx) throw std::invalid_argument("ChaseHipSp: null context");
-        if (N == 0 || nevex_ == 0 || nevex_ > N) throw std::invalid_argument("ChaseHipSp: need 0 < nev+nex <= N");
+        if (N == 0 || nevex_ == 0 || nc_ > N) throw std::invalid_argument("ChaseHipSp: need 0 < nev+nex <= N");
         if (ldh < N || ldv < N) throw std::invalid_argument("ChaseHipSp: leading dimension smaller than N");
         // the reference's single-precision defaults (algorithm/configuration.hpp:58-129)
         config_.SetTol(1e-5); config_.SetDeg(10); config_.SetMaxDeg(18); config_.SetLanczosIter(12);
@@ -45,13 +48,13 @@ public:
         ld_ = shadow_ld(N_);
         if (h_on_device_) { dH_ = H; ldd_h_ = ldh; }
         else { ldd_h_ = ld_; alloc((void**)&dH_, ldd_h_ * N_ * sizeof(ST)); }
-        alloc((void**)&dV1_, ld_ * nevex_ * sizeof(ST));
-        alloc((void**)&dV2_, ld_ * nevex_ * sizeof(ST));
+        alloc((void**)&dV1_, ld_ * nc_ * sizeof(ST));
+        alloc((void**)&dV2_, ld_ * nc_ * sizeof(ST));
         alloc((void**)&dD0_, N_ * sizeof(ST));
-        alloc((void**)&dW_, N_ * nevex_ * sizeof(T));
-        w_cols_ = nevex_;
-        alloc((void**)&dA_, nevex_ * nevex_ * sizeof(T));
-        alloc((void**)&dAs_, nevex_ * nevex_ * sizeof(ST));
+        alloc((void**)&dW_, N_ * nc_ * sizeof(T));
+        w_cols_ = nc_;
+        alloc((void**)&dA_, (a_elems ? a_elems : nc_ * nc_) * sizeof(T));
+        alloc((void**)&dAs_, nc_ * nc_ * sizeof(ST));
     }
     ~ChaseHipSp() override
     {
@@ -64,7 +67,7 @@ public:
     std::size_t GetNex() override { return nex_; }
     std::size_t GetLanczosIter() override { return lanczosIter_; }
     std::size_t GetNumLanczos() override { return numLanczos_; }
-    std::size_t GetRitzvBlockSize() const override { return nevex_; }
+    std::size_t GetRitzvBlockSize() const override { return nc_; }
     R* GetRitzv() override { return ritzv_; }
     R* GetResid() override { return resid_.data(); }
     ConfigT& GetConfig() override { return config_; }
@@ -156,11 +159,12 @@ public:
         if (random) {
             std::mt19937 gen(1337.0);
             std::normal_distribution<> d;
-            for (std::size_t j = 0; j < nevex_; ++j)
+            for (std::size_t j = 0; j < nc_; ++j)
                 for (std::size_t i = 0; i < N_; ++i) V1_[i + j * ldv_] = rnd(d, gen);
         }
-        hip_ok(chase_hip_upload_matrix_sp(ctx_, CP, (int)N_, (int)nevex_, V1_, (long)ldv_, dV1_, (long)ld_), "upload V");
-        hip_ok(chase_hip_lacpy_sp(ctx_, CP, (int)N_, (int)nevex_, dV1_, (long)ld_, dV2_, (long)ld_), "lacpy_sp");
+        hip_ok(chase_hip_upload_matrix_sp(ctx_, CP, (int)N_, (int)nc_, V1_, (long)ldv_, dV1_, (long)ld_), "upload V");
+        init_vecs_hook(random);
+        hip_ok(chase_hip_lacpy_sp(ctx_, CP, (int)N_, (int)nc_, dV1_, (long)ld_, dV2_, (long)ld_), "lacpy_sp");
         reset_perm();
         upload_H();
     }
@@ -176,7 +180,7 @@ public:
         std::vector<ST> h(N_);
         for (std::size_t c = 0; c < n_indices; ++c) {
             const std::size_t j = fixednev + col_indices[c];
-            if (j >= nevex_) throw std::invalid_argument("ReinitColumns: column out of range");
+            if (j >= nc_) throw std::invalid_argument("ReinitColumns: column out of range");
             for (auto& x : h) x = rnd(d, gen);
             hip_ok(chase_hip_upload_matrix_sp(ctx_, CP, (int)N_, 1, h.data(), (long)N_, dV1_ + j * ld_, (long)ld_), "upload column");
             hip_ok(chase_hip_lacpy_sp(ctx_, CP, (int)N_, 1, dV1_ + j * ld_, (long)ld_, dV2_ + j * ld_, (long)ld_), "lacpy_sp");
@@ -187,7 +191,7 @@ public:
     {
         CHASE_PHASE(ctx_, "End");
         flush_swaps();
-        hip_ok(chase_hip_download_matrix_sp(ctx_, CP, (int)N_, (int)nevex_, dV1_, (long)ld_, V1_, (long)ldv_), "download V");
+        hip_ok(chase_hip_download_matrix_sp(ctx_, CP, (int)N_, (int)nc_, dV1_, (long)ld_, V1_, (long)ldv_), "download V");
     }
 
     // ---- filter --------------------------------------------------------------------------------------------------
@@ -242,27 +246,7 @@ public:
         CHASE_PHASE(ctx_, "QR");
         flush_swaps();
         hip_ok(chase_hip_lacpy_sp(ctx_, CP, (int)N_, (int)locked_, dV1_, (long)ld_, dV2_, (long)ld_), "lacpy_sp");
-        hip_ok(chase_hip_convert_s2d(ctx_, CP, (int)N_, (int)nevex_, dV1_, (long)ld_, dW_, (long)N_), "convert_s2d");
-        int disable = config_.DoCholQR() ? 0 : 1;
-        if (const char* s = std::getenv("CHASE_DISABLE_CHOLQR")) disable = std::atoi(s);
-        R thld_hi = 1e4, thld_lo = 1e1;                 // chase_gpu.hpp:808-809, float
-        if (const char* s = std::getenv("CHASE_CHOLQR1_THLD")) thld_lo = std::atof(s);
-        last_qr_variant_ = 0;
-        if (disable == 1 && cond != (R)1.0) {
-            hip_ok(chase_hip_houseqr(ctx_, CP, (int)N_, (int)nevex_, dW_, (long)N_), "houseqr");
-        } else {
-            const int variant = (cond > thld_hi) ? 3 : (cond < thld_lo ? 1 : 2);
-            last_qr_variant_ = variant;
-            const int info = chase_hip_cholqr(ctx_, CP, (int)N_, (int)nevex_, dW_, (long)N_, dA_, (long)nevex_, variant, (long)N_);
-            hip_ok(info, "cholqr");
-            if (info != 0) {
-                last_qr_variant_ = 0;
-                // a failed factorisation leaves the block as it was (cholqr1.hpp:41-68): Householder on the same widened columns
-                hip_ok(chase_hip_convert_s2d(ctx_, CP, (int)N_, (int)nevex_, dV1_, (long)ld_, dW_, (long)N_), "convert_s2d");
-                hip_ok(chase_hip_houseqr(ctx_, CP, (int)N_, (int)nevex_, dW_, (long)N_), "houseqr");
-            }
-        }
-        hip_ok(chase_hip_convert_d2s(ctx_, CP, (int)N_, (int)nevex_, dW_, (long)N_, dV1_, (long)ld_), "convert_d2s");
+        qr_block(cond);
         hip_ok(chase_hip_lacpy_sp(ctx_, CP, (int)N_, (int)locked_, dV2_, (long)ld_, dV1_, (long)ld_), "lacpy_sp");
     }
 
@@ -298,7 +282,7 @@ public:
     void recompute_residuals(std::size_t ncols, const double* lambda, double* out) override
     {
         CHASE_PHASE(ctx_, "recompute_residuals");
-        if (ncols > nevex_) throw std::invalid_argument("recompute_residuals: more columns than the Impl holds");
+        if (ncols > nc_) throw std::invalid_argument("recompute_residuals: more columns than the Impl holds");
         flush_swaps();
         if (!h_resident_) upload_H();
         gemm32(N_, ncols, N_, T(1), dH_, ldd_h_, dV1_, ld_, T(0), dV2_, ld_);             // dV2_ is scratch from here on
@@ -308,7 +292,7 @@ public:
     void Swap(std::size_t i, std::size_t j) override
     {
         if (i == j) return;
-        if (i >= nevex_ || j >= nevex_) throw std::invalid_argument("Swap: column out of range");
+        if (i >= nc_ || j >= nc_) throw std::invalid_argument("Swap: column out of range");
         std::swap(perm_[i], perm_[j]);
         perm_dirty_ = true;
     }
@@ -337,7 +321,7 @@ public:
     {
         CHASE_PHASE(ctx_, "LanczosDos");
         flush_swaps();
-        if (m > nevex_ || idx > m) throw std::invalid_argument("LanczosDos: more Lanczos vectors than the block holds");
+        if (m > nc_ || idx > m) throw std::invalid_argument("LanczosDos: more Lanczos vectors than the block holds");
         hip_ok(chase_hip_upload_matrix(ctx_, CP, (int)m, (int)idx, ritzVc, (long)m, dA_, (long)m), "upload ritzV");
         hip_ok(chase_hip_convert_d2s(ctx_, CP, (int)m, (int)idx, dA_, (long)m, dAs_, (long)m), "convert_d2s");
         gemm32w('N', N_, idx, m, dV1_, ld_, dAs_, m, dW_, N_);
@@ -346,18 +330,52 @@ public:
         hip_ok(chase_hip_lacpy_sp(ctx_, CP, (int)N_, (int)(m - idx), dV2_ + idx * ld_, (long)ld_, dV1_ + idx * ld_, (long)ld_), "lacpy_sp");
     }
 
-    // the current block widened to fp64 on the host (N x (nev+nex), ld): what chase_hip_solver_peek_v returns
+    // the current block widened to fp64 on the host (N x all columns of the block, ld): what chase_hip_solver_peek_v returns
     void peek_widened(T* host, std::size_t ld)
     {
         flush_swaps();
         if (ld < N_) throw std::invalid_argument("peek_v: leading dimension smaller than N");
-        std::vector<ST> h(N_ * nevex_);
-        hip_ok(chase_hip_download_matrix_sp(ctx_, CP, (int)N_, (int)nevex_, dV1_, (long)ld_, h.data(), (long)N_), "download V");
-        for (std::size_t j = 0; j < nevex_; ++j)
+        std::vector<ST> h(N_ * nc_);
+        hip_ok(chase_hip_download_matrix_sp(ctx_, CP, (int)N_, (int)nc_, dV1_, (long)ld_, h.data(), (long)N_), "download V");
+        for (std::size_t j = 0; j < nc_; ++j)
             for (std::size_t i = 0; i < N_; ++i) host[i + j * ld] = T(h[i + j * N_]);
     }
 
-private:
+protected:
+    // after the start block is uploaded, before it is mirrored to V2 (the pseudo-Hermitian Impl damps the lower rows)
+    virtual void init_vecs_hook(bool) {}
+    // after all columns of V1 are widened into dW_, before they are factorised (the pseudo-Hermitian Impl flips the locked ones)
+    virtual void qr_widened_hook() {}
+
+    // QR_DOUBLE_PRECISION on all nc_ columns of V1: widened into the fp64 scratch, CholQR1 / CholQR2 / shifted CholQR2 or Householder
+    // there with the single-precision thresholds, rounded back
+    void qr_block(R cond)
+    {
+        hip_ok(chase_hip_convert_s2d(ctx_, CP, (int)N_, (int)nc_, dV1_, (long)ld_, dW_, (long)N_), "convert_s2d");
+        qr_widened_hook();
+        int disable = config_.DoCholQR() ? 0 : 1;
+        if (const char* s = std::getenv("CHASE_DISABLE_CHOLQR")) disable = std::atoi(s);
+        R thld_hi = 1e4, thld_lo = 1e1;                 // chase_gpu.hpp:808-809, float
+        if (const char* s = std::getenv("CHASE_CHOLQR1_THLD")) thld_lo = std::atof(s);
+        last_qr_variant_ = 0;
+        if (disable == 1 && cond != (R)1.0) {
+            hip_ok(chase_hip_houseqr(ctx_, CP, (int)N_, (int)nc_, dW_, (long)N_), "houseqr");
+        } else {
+            const int variant = (cond > thld_hi) ? 3 : (cond < thld_lo ? 1 : 2);
+            last_qr_variant_ = variant;
+            const int info = chase_hip_cholqr(ctx_, CP, (int)N_, (int)nc_, dW_, (long)N_, dA_, (long)nc_, variant, (long)N_);
+            hip_ok(info, "cholqr");
+            if (info != 0) {
+                last_qr_variant_ = 0;
+                // a failed factorisation leaves the block as it was (cholqr1.hpp:41-68): Householder on the same widened columns
+                hip_ok(chase_hip_convert_s2d(ctx_, CP, (int)N_, (int)nc_, dV1_, (long)ld_, dW_, (long)N_), "convert_s2d");
+                qr_widened_hook();
+                hip_ok(chase_hip_houseqr(ctx_, CP, (int)N_, (int)nc_, dW_, (long)N_), "houseqr");
+            }
+        }
+        hip_ok(chase_hip_convert_d2s(ctx_, CP, (int)N_, (int)nc_, dW_, (long)N_, dV1_, (long)ld_), "convert_d2s");
+    }
+
     static ST rnd(std::normal_distribution<>& d, std::mt19937& g)
     {
         if constexpr (is_cplx<T>::value) { const double re = d(g); const double im = d(g); return ST((float)re, (float)im); }
@@ -408,7 +426,7 @@ private:
     }
     void reset_perm()
     {
-        for (std::size_t i = 0; i < nevex_; ++i) perm_[i] = (int)i;
+        for (std::size_t i = 0; i < nc_; ++i) perm_[i] = (int)i;
         perm_dirty_ = false;
     }
     // apply the deferred swaps: V1'[:, j] = V1[:, perm[j]] through V2 (free whenever swaps are pending)
@@ -416,7 +434,7 @@ private:
     {
         if (!perm_dirty_) return;
         std::vector<int> src, dst;
-        for (std::size_t j = 0; j < nevex_; ++j)
+        for (std::size_t j = 0; j < nc_; ++j)
             if (perm_[j] != (int)j) { src.push_back(perm_[j]); dst.push_back((int)j); }
         if (!src.empty())
             hip_ok(chase_hip_permute_cols_sp(ctx_, CP, (int)N_, dV1_, (long)ld_, dV2_, (long)ld_, src.data(), dst.data(),
@@ -501,7 +519,7 @@ private:
     }
 
     chase_hip_ctx* ctx_;
-    std::size_t N_, nev_, nex_, nevex_;
+    std::size_t N_, nev_, nex_, nevex_, nc_;          // nc_: columns of the vector blocks (nevex_ here, 2 nevex_ pseudo-Hermitian)
     ST* H_; std::size_t ldh_;
     ST* V1_; std::size_t ldv_;
     R* ritzv_;

@@ -13,6 +13,7 @@
 #include "pchase_hip_impl.hpp"
 #include "chase_hip_pseudo_impl.hpp"
 #include "chase_hip_sp_impl.hpp"
+#include "chase_hip_sp_pseudo_impl.hpp"
 #include "pchase_hip_pseudo_impl.hpp"
 #include "tape.hpp"
 
@@ -28,8 +29,9 @@ struct chase_hip_solver {
     pChaseHip<double>* pd = nullptr;                // set for the distributed Impl only
     pChaseHip<zc>* pz = nullptr;
     ChaseHipSp<double>* sd = nullptr;               // set for the single-precision Impl only: its blocks are fp32
-    ChaseHipSp<zc>* sz = nullptr;
+    ChaseHipSp<zc>* sz = nullptr;                   // (ChaseHipSpPseudo is one of them: pseudo is set as well)
     bool sp() const { return sd || sz; }
+    const char* sp_name() const { return pseudo ? "single-precision pseudo-Hermitian solver" : "single-precision solver"; }
     SolveStats stats;
     CallTrace trace;
     std::string trace_text;
@@ -129,6 +131,33 @@ int chase_hip_solver_create_pseudo(chase_hip_solver** out, chase_hip_ctx* ctx, i
     return 0;
 }
 
+/* single-precision pseudo-Hermitian (BSE) Impl: H and V are fp32 / complex fp32, V is N x 2*(nev+nex), ritzv has 2*(nev+nex)
+ * doubles; the reference's float defaults */
+int chase_hip_solver_create_pseudo_sp(chase_hip_solver** out, chase_hip_ctx* ctx, int cplx, size_t N, size_t nev, size_t nex,
+                                      const void* H32, size_t ldh, void* V32, size_t ldv, double* ritzv, int h_on_device)
+{
+    if (!out || !ctx || !H32 || !V32 || !ritzv)
+        return chase_hip::set_error(CHASE_HIP_EINVAL, "solver_create_pseudo_sp: NULL argument");
+    auto s = std::make_unique<chase_hip_solver>();
+    s->cplx = cplx ? 1 : 0;
+    s->pseudo = 1;
+    chase_hip_host_lapack_warmup();          // not fatal here: a missing provider is reported by the first LAPACK call
+    using cf = std::complex<float>;
+    int rc = guarded("solver_create_pseudo_sp", [&] {
+        if (cplx) {
+            auto* p = new ChaseHipSpPseudo<zc>(ctx, N, nev, nex, (cf*)const_cast<void*>(H32), ldh, (cf*)V32, ldv, ritzv, h_on_device != 0);
+            s->z.reset(p); s->ex = p; s->sz = p;
+        } else {
+            auto* p = new ChaseHipSpPseudo<double>(ctx, N, nev, nex, (float*)const_cast<void*>(H32), ldh, (float*)V32, ldv, ritzv,
+                                                   h_on_device != 0);
+            s->d.reset(p); s->ex = p; s->sd = p;
+        }
+    });
+    if (rc) return rc;
+    *out = s.release();
+    return 0;
+}
+
 int chase_hip_psolver_create(chase_hip_solver** out, chase_hip_ctx* ctx, chase_hip_grid* grid, int cplx, size_t N,
                              size_t nev, size_t nex, size_t mb, size_t nb, void* H_loc_dev, size_t ldh, double* ritzv)
 {
@@ -214,8 +243,8 @@ int chase_hip_solver_set(chase_hip_solver* s, const char* key, double v)
     int rc = 0;
     if (s->sp() && v != 0.0 &&
         (name == "mixed_precision" || name == "sp_product" || name == "sp_prepack" || name == "h2_mixed_precision"))
-        return chase_hip::set_error(CHASE_HIP_EINVAL, ("solver_set: " + name + " = 1 does not exist on the single-precision solver "
-                                                       "(every product of it is the fp32 MFMA one)").c_str());
+        return chase_hip::set_error(CHASE_HIP_EINVAL, ("solver_set: " + name + " = 1 does not exist on the " + s->sp_name() +
+                                                       " (every product of it is the fp32 MFMA one)").c_str());
     const int grc = guarded("solver_set", [&] { DISPATCH(s, {
         auto& c = k.GetConfig();
         if (name == "tol") c.SetTol(v);
@@ -339,7 +368,7 @@ int chase_hip_solver_solve(chase_hip_solver* s, int record_trace)
 {
     if (!s) return chase_hip::set_error(CHASE_HIP_EINVAL, "solver_solve: NULL solver");
     if (s->sp() && s->tape_mode)
-        return chase_hip::set_error(CHASE_HIP_EINVAL, "solver_solve: the single-precision solver has no tape modes");
+        return chase_hip::set_error(CHASE_HIP_EINVAL, (std::string("solver_solve: the ") + s->sp_name() + " has no tape modes").c_str());
     s->stats = SolveStats();
     s->trace.lines.clear();
     s->trace.enabled = record_trace != 0;
@@ -380,7 +409,7 @@ int chase_hip_solver_tape_mode(chase_hip_solver* s, int mode)
 {
     if (!s || mode < 0 || mode > 2) return chase_hip::set_error(CHASE_HIP_EINVAL, "tape_mode: 0, 1 or 2");
     if (s->sp() && mode != 0)
-        return chase_hip::set_error(CHASE_HIP_EINVAL, "tape_mode: the single-precision solver has no tape modes");
+        return chase_hip::set_error(CHASE_HIP_EINVAL, (std::string("tape_mode: the ") + s->sp_name() + " has no tape modes").c_str());
     s->tape_mode = mode;
     return 0;
 }
@@ -546,7 +575,8 @@ int chase_hip_solver_recompute_residuals(chase_hip_solver* s, size_t ncols, cons
 int chase_hip_solver_hash_v(chase_hip_solver* s, chase_hip_ctx* ctx, size_t ncols, unsigned long long* hash)
 {
     if (!s || !ctx || !hash) return chase_hip::set_error(CHASE_HIP_EINVAL, "hash_v: NULL argument");
-    if (s->sp()) return chase_hip::set_error(CHASE_HIP_EINVAL, "hash_v: not on the single-precision solver (its block is fp32)");
+    if (s->sp())
+        return chase_hip::set_error(CHASE_HIP_EINVAL, (std::string("hash_v: not on the ") + s->sp_name() + " (its block is fp32)").c_str());
     return guarded("hash_v", [&] {
         DISPATCH(s, {
             if (ncols > k.GetRitzvBlockSize()) throw std::invalid_argument("more columns than the Impl holds");

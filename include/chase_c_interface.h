@@ -15,8 +15,11 @@
  * The GPU is chosen by CHASE_HIP_DEVICE (default 0).
  *   schase_* / cchase_* : the same sequence in single precision (interface/chase_c_interface.h:19-41,178-212): H, V and ritzv
  *              are float / float _Complex / float, tol is a float; served by the single-precision solver
- *              (chase_hip_solver_create_sp), whose Ritz values are converted at this boundary.  The pseudo-Hermitian
- *              cchase_*pseudo* names and the p[sc]chase grid names are not provided.
+ *              (chase_hip_solver_create_sp), whose Ritz values are converted at this boundary.
+ *   cchase_init_pseudo_[internal_] / cchase_pseudo_ : single-precision pseudo-Hermitian problems (:46-57) on
+ *              chase_hip_solver_create_pseudo_sp; V has 2*(nev+nex) columns, ritzv 2*(nev+nex) floats; the slot rules are those of z:
+ *              cchase_ solves whichever type was initialised, cchase_get_eigenpairs_ / cchase_finalize_ serve whichever is live.
+ *              The p[sc]chase grid names are not provided.
  *
  * Distributed entry points (interface/chase_c_interface.h:61-65,95-99,126-128,149,177-195): every p?chase_init* of the
  * reference takes an MPI_Comm* and builds the 2D grid from it.  libchase_hip.so exports the same entry points with the
@@ -53,6 +56,9 @@ void schase_finalize_(int* flag);
 void schase_get_eigenpairs_(float* LEigsV, int* ld, float* ritzv);
 void cchase_init_(int* N, int* nev, int* nex, void* H, int* ldh, void* V, float* ritzv, int* init);
 void cchase_init_internal_(int* N, int* nev, int* nex, void* H, int* ldh, int* init);
+void cchase_init_pseudo_(int* N, int* nev, int* nex, void* H, int* ldh, void* V, float* ritzv, int* init);
+void cchase_init_pseudo_internal_(int* N, int* nev, int* nex, void* H, int* ldh, int* init);
+void cchase_pseudo_(int* deg, float* tol, char* mode, char* opt, char* qr);
 void cchase_(int* deg, float* tol, char* mode, char* opt, char* qr);
 void cchase_finalize_(int* flag);
 void cchase_get_eigenpairs_(void* LEigsV, int* ld, float* ritzv);
@@ -93,7 +99,7 @@ struct chase_hip_solver* chase_hip_cshim_dist_solver(int cplx); /* the live dist
  * thread per GPU) with a solver of its own; 0 (default): ONE solver per type in the process, replaced by the next init from
  * any thread - the reference's static members (interface/chase_c_interface.cpp:905-1290).  Returns the previous setting. */
 int chase_hip_cshim_thread_ranks(int on);
-struct chase_hip_solver* chase_hip_cshim_seq_solver(int kind); /* live sequential solver: 0 real, 1 complex, 2 complex pseudo-Hermitian, 3 / 4 single-precision real / complex */
+struct chase_hip_solver* chase_hip_cshim_seq_solver(int kind); /* live sequential solver: 0 real, 1 complex, 2 complex pseudo-Hermitian, 3 / 4 single-precision real / complex, 5 single-precision complex pseudo-Hermitian */
 void pdchase_init_hip_(int* N, int* nev, int* nex, int* m, int* n, double* H, int* ldh, double* V, double* ritzv,
                        struct chase_hip_grid* grid, int* init);
 void pdchase_init_internal_hip_(int* N, int* nev, int* nex, int* m, int* n, double* H, int* ldh,

@@ -353,6 +353,14 @@ int chase_hip_shift_diag_sp(chase_hip_ctx* ctx, int cplx, int n, void* H, long l
  * formed and their squares summed in fp64 (fixed order: bitwise reproducible).  lambda_host, resid_host: n doubles on the host */
 int chase_hip_resid_norms_sp(chase_hip_ctx* ctx, int cplx, int m, int n, const void* W, long ldw, const void* V, long ldv,
                              const double* lambda_host, double* resid_host);
+/* X[i, j] *= s for row0 <= i < m, j < n on fp32 (cplx: complex fp32) columns: one IEEE fp32 multiply per component (both
+ * components of a complex entry times the real s), no other arithmetic: s = -1 is the exact sign flip.  0 <= row0 <= m; row0 == m
+ * does nothing.  The fp32 twin of chase_hip_scale_rows */
+int chase_hip_scale_rows_sp(chase_hip_ctx* ctx, int cplx, int m, int n, void* X, long ldx, int row0, float s);
+/* The K-conjugate of n fp32 (cplx: complex fp32) columns of N rows (N even, h = N/2): second[i + h, j] = conj(first[i, j]) and
+ * second[i, j] = conj(first[i + h, j]) for i < h; real: the plain half swap.  Exact.  first and second are disjoint column ranges
+ * (they may belong to one block).  Replaces two lacpy calls and a conj (chase_cpu.hpp:557-588) */
+int chase_hip_kconj_sp(chase_hip_ctx* ctx, int cplx, int N, int n, const void* first, long ldf, void* second, long lds);
 /* the fp32 twins of lacpy, swap_cols, permute_cols, upload_matrix, download_matrix and complete_hermitian (same contracts) */
 int chase_hip_lacpy_sp(chase_hip_ctx* ctx, int cplx, int m, int n, const void* A, long lda, void* B, long ldb);
 int chase_hip_swap_cols_sp(chase_hip_ctx* ctx, int cplx, int m, void* V, long ldv, long i, long j);

@@ -46,6 +46,18 @@ int chase_hip_solver_create_pseudo(chase_hip_solver** out, chase_hip_ctx* ctx, i
  * there; their environment variables are ignored).  chase_hip_solver_peek_v returns the block widened to fp64. */
 int chase_hip_solver_create_sp(chase_hip_solver** out, chase_hip_ctx* ctx, int cplx, size_t N, size_t nev, size_t nex,
                                const void* H32, size_t ldh, void* V32, size_t ldv, double* ritzv, int h_on_device);
+/* Single-precision pseudo-Hermitian (Bethe-Salpeter) Impl (ChaseHipSpPseudo, chase_amd/host/chase_hip_sp_pseudo_impl.hpp; the
+ * reference's ChASEGPU<complex<float>, PseudoHermitianMatrix> and its real twin): the contract of chase_hip_solver_create_pseudo
+ * (N even, 2 (nev+nex) <= N, V32 is N x 2*(nev+nex), ritzv holds 2*(nev+nex) doubles) on the data of chase_hip_solver_create_sp:
+ * H32 and V32 are fp32 (cplx: complex fp32) and stay fp32 on the device, h_on_device != 0 uses the device matrix in place at any
+ * ldh >= N, no fp64 copy of H is ever made, the float defaults apply.  chase_hip_solver_solve runs chase::Solve_pseudo.  The H^2
+ * filter step is two chase_hip_gemm_s / _c products and chase_hip_axpy_sp (hemm_sp_calls += 2 per step, hemm_calls stays 0); QR
+ * runs in fp64 on the widened block (locked columns keep their fp32 bits); Rayleigh-Ritz forms S H Q in fp32, projects into fp64,
+ * runs the dense core in fp64 and rounds the eigenvectors; residual norms are summed in fp64.  The same entry points refuse as on
+ * the single-precision Hermitian handle: tape modes, chase_hip_solver_hash_v, device_rng = 1 and a 1 for any of the four precision
+ * switches return CHASE_HIP_EINVAL.  chase_hip_solver_peek_v returns all 2*(nev+nex) columns widened to fp64. */
+int chase_hip_solver_create_pseudo_sp(chase_hip_solver** out, chase_hip_ctx* ctx, int cplx, size_t N, size_t nev, size_t nex,
+                                      const void* H32, size_t ldh, void* V32, size_t ldv, double* ritzv, int h_on_device);
 /* Distributed Impl (pChASECPU / pChASEGPU constructor contract, pchase_cpu.hpp:92-93): H_loc is this rank's DEVICE
  * block of the N x N matrix, distributed block-cyclically with (mb, nb) over the grid (mb = nb = 0: the reference's block
  * layout); the nev+nex vectors live distributed on the devices (chase_hip_psolver_{upload,download}_v move a rank's
@@ -101,7 +113,7 @@ int chase_hip_solver_destroy(chase_hip_solver* s);
  * touched.  H^2 carries its shift in gamma, so the shadow of H is converted once per resident matrix.  Counted in hemm_sp_calls
  * (two per step), hemm_sp_vecs, sp_filters; get additionally: sp_h_converts (whole-matrix conversions of H; cleared by
  * reset_counters).
- * On a single-precision solver (chase_hip_solver_create_sp) a 1 for mixed_precision, sp_product, sp_prepack or h2_mixed_precision
+ * On a single-precision solver (chase_hip_solver_create_sp, chase_hip_solver_create_pseudo_sp) a 1 for mixed_precision, sp_product, sp_prepack or h2_mixed_precision
  * returns CHASE_HIP_EINVAL (0 is accepted), and CHASE_HIP_MIXED_PRECISION / _SP_PRODUCT / _SP_PREPACK are not read.
  * device_bytes (get only; the single-GPU solvers - CHASE_HIP_EINVAL on a grid): the sum of the Impl's own device allocations (H
  * unless it is the caller's, the vector blocks, scratch, shadows made so far; transient Lanczos workspace is not in it). */
