@@ -93,6 +93,11 @@ _sig("chase_hip_mfma_f64_peak", c_int, c_void_p, P(c_double))
 _sig("chase_hip_gemm3m_enabled", c_int)
 _sig("chase_hip_host_lapack_warmup", c_int)
 _sig("chase_hip_hbm_copy_peak", c_int, c_void_p, c_size_t, P(c_double))
+_sig("chase_hip_trsm_left_upper", c_int, c_void_p, c_int, c_char, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_potrf_upper_blocked", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_int)
+_sig("chase_hip_hegst_upper", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_int)
+_sig("chase_hip_gev_reduce", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_gev_backtransform", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
 
 
 def check(code, where):
@@ -356,6 +361,29 @@ class Context:
         g = c_double()
         check(lib.chase_hip_hbm_copy_peak(self.h, nbytes, C.byref(g)), "hbm_copy_peak")
         return g.value
+
+    # ---- generalized problem H x = lambda S x (capi_gev.hip); device addresses (ints), leading dimensions in elements ----
+    def trsm_left_upper(self, op, n, nrhs, R, ldr, B, ldb, cplx):
+        """B <- op(R)^{-1} B, R upper triangular, op 'N' or 'C'"""
+        check(lib.chase_hip_trsm_left_upper(self.h, int(cplx), op.encode()[0:1], n, nrhs, R, ldr, B, ldb), "trsm_left_upper")
+
+    def potrf_upper_blocked(self, n, A, lda, cplx, outer_nb=0):
+        """In-place upper Cholesky that leaves the strictly lower triangle alone; returns the LAPACK info (0, or the first bad pivot)"""
+        info = lib.chase_hip_potrf_upper_blocked(self.h, int(cplx), n, A, lda, outer_nb)
+        return info if info >= 0 else check(info, "potrf_upper_blocked")
+
+    def hegst_upper(self, n, A, lda, U, ldu, cplx, nb=0):
+        """A <- U^{-H} A U^{-1}, exactly Hermitian, both triangles"""
+        check(lib.chase_hip_hegst_upper(self.h, int(cplx), n, A, lda, U, ldu, nb), "hegst_upper")
+
+    def gev_reduce(self, n, A, lda, S, lds, cplx):
+        """S <- U (S = U^H U), A <- U^{-H} A U^{-1}; returns 0 or the pivot at which S is not positive definite (A untouched)"""
+        info = lib.chase_hip_gev_reduce(self.h, int(cplx), n, A, lda, S, lds)
+        return info if info >= 0 else check(info, "gev_reduce")
+
+    def gev_backtransform(self, n, ncols, U, ldu, X, ldx, cplx):
+        """X <- U^{-1} X"""
+        check(lib.chase_hip_gev_backtransform(self.h, int(cplx), n, ncols, U, ldu, X, ldx), "gev_backtransform")
 
 
 # ---- non-GEMM kernels -------------------------------------------------------------------------------------------------
@@ -701,6 +729,90 @@ class Solver:
 
     def symOrHermMatrix(self, uplo):
         check(lib.chase_hip_op_sym_or_herm(self.h, uplo.encode()[0:1]), "symOrHermMatrix")
+
+
+class GevSolver:
+    """The lowest nev pairs of the generalized Hermitian-definite problem H x = lambda S x (fp64, one GPU).  H and S (Fortran
+    order, S positive definite; the upper triangles are what is read) are uploaded and reduced in place on the device:
+    S = U^H U, C = U^{-H} H U^{-1}; an ordinary Solver then works on C where it lies (self.solver).  While this object lives the
+    device holds C and U, 2 N^2 elements.  set / get / solve / stats / resid are the Solver's; eigenpairs() gives the Ritz values
+    and the back-transformed, S-orthonormal vectors X = U^{-1} Y.  S not positive definite: ChaseHipError whose code (and
+    .pivot) is the index of the first non-positive pivot."""
+
+    def __init__(self, ctx, H, S, nev, nex):
+        assert H.ndim == 2 and H.shape[0] == H.shape[1] and S.shape == H.shape
+        self.ctx = ctx
+        self.cplx = bool(np.iscomplexobj(H) or np.iscomplexobj(S))
+        self.N, self.nev, self.nex = H.shape[0], nev, nex
+        self.H, self.S = H, S                              # the originals, for gev_residuals()
+        self.dC, self.dU = ctx.array(H.astype(self._dt(), copy=False)), ctx.array(S.astype(self._dt(), copy=False))
+        self.solver = None
+        info = ctx.gev_reduce(self.N, self.dC.ptr, self.N, self.dU.ptr, self.N, self.cplx)
+        if info > 0:
+            self.close()
+            err = ChaseHipError(info, "gev_reduce", f"S is not positive definite: pivot {info} is not positive")
+            err.pivot = info
+            raise err
+        self.solver = Solver(ctx, None, nev, nex, h_on_device_ptr=self.dC.ptr, N=self.N, cplx=self.cplx)
+
+    def _dt(self):
+        return np.complex128 if self.cplx else np.float64
+
+    def close(self):
+        if self.solver:
+            self.solver.close()
+            self.solver = None
+        for d in (self.dC, self.dU):
+            if d is not None:
+                d.free()
+        self.dC = self.dU = None
+
+    def set(self, **kw): self.solver.set(**kw)
+    def get(self, key): return self.solver.get(key)
+    def solve(self, trace=False): return self.solver.solve(trace)
+    def stats(self): return self.solver.stats()
+    def resid(self): return self.solver.resid()
+
+    @property
+    def ritzv(self):
+        return self.solver.ritzv
+
+    def reduced(self):
+        """the reduced matrix C as it lies on the device"""
+        return self.dC.download()
+
+    def factor(self):
+        """U in the upper triangle (below it: what S held)"""
+        return self.dU.download()
+
+    def eigenpairs(self):
+        """(lambda[:nev], X[:, :nev]) with H X = S X diag(lambda), X^H S X = I"""
+        dX = self.ctx.array(self.solver.V[:, :self.nev])
+        self.ctx.gev_backtransform(self.N, self.nev, self.dU.ptr, self.N, dX.ptr, self.N, self.cplx)
+        X = dX.download()
+        dX.free()
+        return self.solver.ritzv[:self.nev].copy(), X
+
+    def gev_residuals(self):
+        """|| H x_j - lambda_j S x_j ||_2, j < nev, from fresh four-multiplication products (phase 3) with the ORIGINAL H and S,
+        which are uploaded again for this (two more N^2 blocks while it runs)"""
+        lam, X = self.eigenpairs()
+        n, k, dt = self.N, self.nev, self._dt()
+        full = lambda A: np.triu(A) + np.triu(A, 1).conj().T          # the triangle the reduction read
+        dH, dS, dX = self.ctx.array(full(self.H).astype(dt)), self.ctx.array(full(self.S).astype(dt)), self.ctx.array(X)
+        dW, dV = self.ctx.empty((n, k), dt), self.ctx.empty((n, k), dt)
+        out = np.zeros(k)
+        try:
+            check(lib.chase_hip_ctx_set_phase(self.ctx.h, 3), "set_phase")
+            self.ctx.gemm("N", n, k, n, 1.0, dH.ptr, n, dX.ptr, n, 0.0, dW.ptr, n, self.cplx)
+            self.ctx.gemm("N", n, k, n, 1.0, dS.ptr, n, dX.ptr, n, 0.0, dV.ptr, n, self.cplx)
+            check(lib.chase_hip_resid_norms(self.ctx.h, int(self.cplx), n, k, dW.ptr, n, dV.ptr, n, lam.ctypes.data,
+                                            out.ctypes.data, 0), "resid_norms")
+        finally:
+            lib.chase_hip_ctx_set_phase(self.ctx.h, 0)
+            for d in (dH, dS, dX, dW, dV):
+                d.free()
+        return out
 
 
 _sig("chase_hip_solver_create_sp", c_int, P(c_void_p), c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_void_p, c_size_t,

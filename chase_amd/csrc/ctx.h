@@ -26,8 +26,10 @@ struct chase_hip_ctx {
     unsigned long long sp_wide_calls = 0, sp_split_calls = 0, sp_pieces = 0;
     void* ws = nullptr;          // split-K slabs, grown on demand
     size_t ws_bytes = 0;
-    enum { BUF_TINV = 0, BUF_PANEL, BUF_SCAL, BUF_LAMBDA, BUF_RR, BUF_EIG, BUF_STEDC, BUF_APPLYQ, NBUF };
-    void* bufs[NBUF] = {};   // device scratch, grown on demand (BUF_EIG / BUF_STEDC: the projected eigensolver's blocks)
+    enum { BUF_TINV = 0, BUF_PANEL, BUF_SCAL, BUF_LAMBDA, BUF_RR, BUF_EIG, BUF_STEDC, BUF_APPLYQ, BUF_GEV_TINV, BUF_GEV_PANEL, BUF_GEV_DIAG, NBUF };
+    // device scratch, grown on demand (BUF_EIG / BUF_STEDC: the projected eigensolver's blocks; BUF_GEV_*: capi_gev.hip, whose
+    // drivers call potrf_upper / trsm_right_upper and so cannot share BUF_TINV / BUF_PANEL with them)
+    void* bufs[NBUF] = {};
     size_t buf_bytes[NBUF] = {};
     void* hstage = nullptr;      // pinned host staging (HEEVD round trip)
     size_t hstage_bytes = 0;

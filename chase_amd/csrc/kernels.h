@@ -135,4 +135,12 @@ int stedc_gpu(chase_hip_ctx* c, int n, const double* d, const double* e, double*
 int potf2_trtri(hipStream_t st, bool cplx, double* A, long lda, int nb, int joff, double* Tinv, int* info_dev);
 int trtri_diag(hipStream_t st, bool cplx, const double* R, long ldr, int n, double* Tinv);
 
+// ---- generalized problem (gev_kernels.hip) ----
+// A_jj <- U_jj^{-H} A_jj U_jj^{-1} for one nb x nb block (nb <= 64, one workgroup) from the upper triangles of both; both
+// triangles of A_jj are written, the lower one the bitwise conjugate of the upper one, imaginary diagonal +0
+int hegs2_diag(hipStream_t st, bool cplx, double* A, long lda, const double* U, long ldu, int nb);
+// dst[i, j] = src[i, j] / dst[i, j] += src[i, j] for i <= j < n (leading dimensions in elements, ept doubles per element)
+int copy_upper(hipStream_t st, const double* src, long ld_src, double* dst, long ld_dst, int n, int ept);
+int add_upper(hipStream_t st, const double* src, long ld_src, double* dst, long ld_dst, int n, int ept);
+
 } // namespace chase_hip

@@ -1,0 +1,80 @@
+// c_interface_gev.cpp — the generalized problem H x = lambda S x for callers of the C interface (include/chase_c_interface.h):
+// ?chase_gev_reduce_ and ?chase_gev_backtransform_ are the ppotrf + phegst and the ptrtrs that the reference's
+// docs/example/gev.rst puts around chase::Solve.  Host pointers in, results in place; the matrices are moved to the device,
+// worked on by capi_gev.hip and moved back.  The intended sequence: reduce -> ?chase_init_ / ?chase_ / ?chase_finalize_ on the
+// reduced H -> backtransform of the eigenvectors with the U that reduce left in S.
+#include <cstdlib>
+#include "../../include/chase_c_interface.h"
+#include "../../include/chase_hip.h"
+
+namespace {
+chase_hip_ctx* g_gev_ctx = nullptr;
+
+bool ensure_ctx()
+{
+    if (g_gev_ctx) return true;
+    int dev = 0;
+    if (const char* e = std::getenv("CHASE_HIP_DEVICE")) dev = std::atoi(e);
+    return chase_hip_ctx_create(&g_gev_ctx, dev, nullptr) == 0;
+}
+
+struct DevMat {                                   // an m x n device copy of a host matrix, ld = m
+    chase_hip_ctx* c;
+    void* p = nullptr;
+    explicit DevMat(chase_hip_ctx* c_) : c(c_) {}
+    ~DevMat() { if (p) chase_hip_free(c, p); }
+    int up(int cplx, int m, int n, const void* host, int ldh)
+    {
+        int rc = chase_hip_malloc(c, &p, (size_t)m * n * (cplx ? 16 : 8));
+        return rc ? rc : chase_hip_upload_matrix(c, cplx, m, n, host, ldh, p, m);
+    }
+    int down(int cplx, int m, int n, void* host, int ldh) { return chase_hip_download_matrix(c, cplx, m, n, p, m, host, ldh); }
+};
+
+void reduce(int cplx, int N, void* H, int ldh, void* S, int lds, int* info)
+{
+    if (!info) return;
+    *info = CHASE_HIP_EINVAL;
+    if (N < 0 || ldh < N || lds < N || (N > 0 && (!H || !S))) return;
+    *info = 0;
+    if (N == 0) return;
+    if (!ensure_ctx()) { *info = CHASE_HIP_ENODEV; return; }
+    DevMat dH(g_gev_ctx), dS(g_gev_ctx);
+    int rc = dH.up(cplx, N, N, H, ldh);
+    if (!rc) rc = dS.up(cplx, N, N, S, lds);
+    if (!rc) rc = chase_hip_gev_reduce(g_gev_ctx, cplx, N, dH.p, N, dS.p, N);
+    if (rc) { *info = rc; return; }               // S not positive definite (rc > 0) or a runtime error: H and S as they were
+    rc = dH.down(cplx, N, N, H, ldh);
+    if (!rc) rc = dS.down(cplx, N, N, S, lds);    // the strictly lower triangle comes back as it went
+    *info = rc;
+}
+
+void backtransform(int cplx, int N, int ncols, void* U, int ldu, void* V, int ldv, int* info)
+{
+    if (!info) return;
+    *info = CHASE_HIP_EINVAL;
+    if (N < 0 || ncols < 0 || ldu < N || ldv < N || (N > 0 && (!U || (ncols > 0 && !V)))) return;
+    *info = 0;
+    if (N == 0 || ncols == 0) return;
+    if (!ensure_ctx()) { *info = CHASE_HIP_ENODEV; return; }
+    DevMat dU(g_gev_ctx), dV(g_gev_ctx);
+    int rc = dU.up(cplx, N, N, U, ldu);
+    if (!rc) rc = dV.up(cplx, N, ncols, V, ldv);
+    if (!rc) rc = chase_hip_gev_backtransform(g_gev_ctx, cplx, N, ncols, dU.p, N, dV.p, N);
+    if (!rc) rc = dV.down(cplx, N, ncols, V, ldv);
+    *info = rc;
+}
+} // namespace
+
+extern "C" {
+void dchase_gev_reduce_(int* N, double* H, int* ldh, double* S, int* lds, int* info) { reduce(0, *N, H, *ldh, S, *lds, info); }
+void zchase_gev_reduce_(int* N, void* H, int* ldh, void* S, int* lds, int* info) { reduce(1, *N, H, *ldh, S, *lds, info); }
+void dchase_gev_backtransform_(int* N, int* ncols, double* U, int* ldu, double* V, int* ldv, int* info)
+{
+    backtransform(0, *N, *ncols, U, *ldu, V, *ldv, info);
+}
+void zchase_gev_backtransform_(int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info)
+{
+    backtransform(1, *N, *ncols, U, *ldu, V, *ldv, info);
+}
+}

@@ -62,7 +62,19 @@ void cchase_pseudo_(int* deg, float* tol, char* mode, char* opt, char* qr);
 void cchase_(int* deg, float* tol, char* mode, char* opt, char* qr);
 void cchase_finalize_(int* flag);
 void cchase_get_eigenpairs_(void* LEigsV, int* ld, float* ritzv);
-void chase_enable_sym_check_(int* flag);     /* interface/chase_c_interface.cpp:4055: flag kept for callers that set it */
+/* Generalized Hermitian-definite problems H x = lambda S x (fp64, one GPU): the three ScaLAPACK calls of the reference's
+ * docs/example/gev.rst.  Host pointers, in place, every argument by pointer.  reduce: S (Hermitian positive definite, upper
+ * triangle read) becomes its Cholesky factor U in the upper triangle (S = U^H U; the strictly lower triangle is left alone), H
+ * (upper triangle read) becomes U^{-H} H U^{-1}, both triangles, exactly Hermitian.  backtransform: V (N x ncols) <- U^{-1} V.
+ * *info: 0, the index of the first non-positive pivot of S (H and S are then unchanged), or a negative CHASE_HIP_* code.
+ * Sequence: ?chase_gev_reduce_ -> ?chase_init_ / ?chase_ / ?chase_finalize_ on the reduced H -> ?chase_gev_backtransform_ on
+ * the eigenvectors; the Ritz values are those of (H, S), the vectors come out S-orthonormal.  Not provided: grid solvers,
+ * single precision, pseudo-Hermitian problems, itype 2 and 3, and the Y = U X that approximate start vectors would need. */
+void dchase_gev_reduce_(int* N, double* H, int* ldh, double* S, int* lds, int* info);
+void zchase_gev_reduce_(int* N, void* H, int* ldh, void* S, int* lds, int* info);
+void dchase_gev_backtransform_(int* N, int* ncols, double* U, int* ldu, double* V, int* ldv, int* info);
+void zchase_gev_backtransform_(int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info);
+void chase_enable_sym_check_(int* flag);    /* interface/chase_c_interface.cpp:4055: flag kept for callers that set it */
 /* unified configuration setters and build queries (interface/chase_c_interface.h:207-238): act on the live solver instance
  * (sequential or distributed), silent when none is initialised */
 void chase_set_tol_(double* tol);

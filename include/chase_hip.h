@@ -382,6 +382,30 @@ int chase_hip_abs_trace(chase_hip_ctx* ctx, int cplx, int n, const void* A, long
  * triangle is never read and its contents on return are unspecified; rows beyond n (lda > n) are untouched */
 int chase_hip_potrf_upper(chase_hip_ctx* ctx, int cplx, int n, void* A, long lda);
 int chase_hip_trsm_right_upper(chase_hip_ctx* ctx, int cplx, int m, int n, const void* R, long ldr, void* V, long ldv);
+
+/* ---- generalized Hermitian-definite problem H x = lambda S x, S = U^H U (capi_gev.hip): fp64, one GPU, upper storage.  These
+ * are the ppotrf / phegst / ptrtrs of the reference's docs/example/gev.rst.  All products take four multiplications whatever the
+ * context's phase; rows beyond n (padded leading dimensions) are never written; op other than 'N' / 'C', a block size that is
+ * negative or no multiple of 64, a leading dimension below n: CHASE_HIP_EINVAL. ------------------------------------------- */
+/* B (n x nrhs) <- op(R)^{-1} B, R upper triangular, op 'N' or 'C' (real data: the transpose); the strictly lower triangle of R is
+ * never read.  64-row steps with inverted diagonal blocks, long products between blocks of 256 rows. */
+int chase_hip_trsm_left_upper(chase_hip_ctx* ctx, int cplx, char op, int n, int nrhs, const void* R, long ldr, void* B, long ldb);
+/* chase_hip_potrf_upper (same result, same info) in two levels, for matrices of the size of the problem: the strictly lower
+ * triangle is neither read nor written and the trailing updates touch the upper block trapezoid only.  outer_nb: columns per
+ * outer block (0: default 2048); n <= outer_nb is one chase_hip_potrf_upper on a scratch copy. */
+int chase_hip_potrf_upper_blocked(chase_hip_ctx* ctx, int cplx, int n, void* A, long lda, int outer_nb);
+/* A <- U^{-H} A U^{-1} (LAPACK xHEGST, itype 1, uplo 'U').  A is read from its upper triangle only, U likewise.  On return both
+ * triangles of A hold the result, exactly Hermitian: the lower triangle is the bitwise conjugate of the upper one and the
+ * imaginary diagonal is +0.  One block (n <= 64) is reduced in LDS by one workgroup.  nb > 0: the blocked xHEGST recurrence with
+ * panels of nb columns (n^3 / 2 multiply-adds).  nb = 0, the default: two full triangular solves on the completed matrix,
+ * (A U^{-1}) then U^{-H} (.), one triangle kept and mirrored - n^3 multiply-adds, but all in products with long inner dimensions,
+ * and about twice as fast at N = 16384 (profiles/gev.txt). */
+int chase_hip_hegst_upper(chase_hip_ctx* ctx, int cplx, int n, void* A, long lda, const void* U, long ldu, int nb);
+/* potrf_upper_blocked(S), then hegst_upper(A, S).  Returns the potrf info > 0 when S is not positive definite and leaves A
+ * untouched then.  S stays on the device next to A: the reduction needs 2 n^2 elements plus panels. */
+int chase_hip_gev_reduce(chase_hip_ctx* ctx, int cplx, int n, void* A, long lda, void* S, long lds);
+/* X (n x ncols) <- U^{-1} X: the eigenvectors of the reduced problem become those of (H, S), S-orthonormal */
+int chase_hip_gev_backtransform(chase_hip_ctx* ctx, int cplx, int n, int ncols, const void* U, long ldu, void* X, long ldx);
 /* variant 1 = cholQR1, 2 = cholQR2, 3 = shiftedcholQR2 (linalg/internal/cpu/cholqr1.hpp:41-189); returns info */
 int chase_hip_cholqr(chase_hip_ctx* ctx, int cplx, int m, int n, void* V, long ldv, void* A, long lda, int variant,
                      long m_global);
