@@ -98,6 +98,11 @@ _sig("chase_hip_potrf_upper_blocked", c_int, c_void_p, c_int, c_int, c_void_p, c
 _sig("chase_hip_hegst_upper", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_int)
 _sig("chase_hip_gev_reduce", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
 _sig("chase_hip_gev_backtransform", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_trmm_left_upper", c_int, c_void_p, c_int, c_char, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_hegst_product_upper", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_gev_reduce_itype", c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_gev_backtransform_itype", c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_gev_starttransform", c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
 
 
 def check(code, where):
@@ -384,6 +389,28 @@ class Context:
     def gev_backtransform(self, n, ncols, U, ldu, X, ldx, cplx):
         """X <- U^{-1} X"""
         check(lib.chase_hip_gev_backtransform(self.h, int(cplx), n, ncols, U, ldu, X, ldx), "gev_backtransform")
+
+    def trmm_left_upper(self, op, n, ncols, U, ldu, X, ldx, cplx):
+        """X <- op(U) X in place, U upper triangular, op 'N' or 'C'"""
+        check(lib.chase_hip_trmm_left_upper(self.h, int(cplx), op.encode()[0:1], n, ncols, U, ldu, X, ldx), "trmm_left_upper")
+
+    def hegst_product_upper(self, n, A, lda, U, ldu, cplx):
+        """A <- U A U^H, exactly Hermitian, both triangles"""
+        check(lib.chase_hip_hegst_product_upper(self.h, int(cplx), n, A, lda, U, ldu), "hegst_product_upper")
+
+    def gev_reduce_itype(self, itype, factor, n, A, lda, S, lds, cplx):
+        """itype 1: A <- U^{-H} A U^{-1}; 2, 3: A <- U A U^H.  factor 1: S <- U first (returns the bad pivot if there is one);
+        factor 0: S already holds U"""
+        info = lib.chase_hip_gev_reduce_itype(self.h, int(cplx), itype, int(factor), n, A, lda, S, lds)
+        return info if info >= 0 else check(info, "gev_reduce_itype")
+
+    def gev_backtransform_itype(self, itype, n, ncols, U, ldu, X, ldx, cplx):
+        """X <- U^{-1} X (itype 1, 2) or U^H X (itype 3)"""
+        check(lib.chase_hip_gev_backtransform_itype(self.h, int(cplx), itype, n, ncols, U, ldu, X, ldx), "gev_backtransform_itype")
+
+    def gev_starttransform(self, itype, n, ncols, U, ldu, X, ldx, cplx):
+        """X <- U X (itype 1, 2) or U^{-H} X (itype 3): the inverse of gev_backtransform_itype"""
+        check(lib.chase_hip_gev_starttransform(self.h, int(cplx), itype, n, ncols, U, ldu, X, ldx), "gev_starttransform")
 
 
 # ---- non-GEMM kernels -------------------------------------------------------------------------------------------------
@@ -732,28 +759,39 @@ class Solver:
 
 
 class GevSolver:
-    """The lowest nev pairs of the generalized Hermitian-definite problem H x = lambda S x (fp64, one GPU).  H and S (Fortran
-    order, S positive definite; the upper triangles are what is read) are uploaded and reduced in place on the device:
-    S = U^H U, C = U^{-H} H U^{-1}; an ordinary Solver then works on C where it lies (self.solver).  While this object lives the
-    device holds C and U, 2 N^2 elements.  set / get / solve / stats / resid are the Solver's; eigenpairs() gives the Ritz values
-    and the back-transformed, S-orthonormal vectors X = U^{-1} Y.  S not positive definite: ChaseHipError whose code (and
-    .pivot) is the index of the first non-positive pivot."""
+    """The lowest nev pairs of a generalized Hermitian-definite problem (fp64, one GPU): itype 1, H x = lambda S x (the default);
+    itype 2, H S x = lambda x; itype 3, S H x = lambda x.  H and S (Fortran order, S positive definite; the upper triangles are
+    what is read) are uploaded and reduced in place on the device: S = U^H U, C = U^{-H} H U^{-1} (itype 1) or U H U^H (itype 2
+    and 3); an ordinary Solver then works on C where it lies (self.solver).  While this object lives the device holds C and U,
+    2 N^2 elements.  set / get / solve / stats / resid are the Solver's; eigenpairs() gives the Ritz values and the
+    back-transformed vectors, X = U^{-1} Y with X^H S X = I for itype 1 and 2, X = U^H Y with X^H S^{-1} X = I for itype 3.
+    update(H, S) moves on to the next pencil of a sequence with the previous vectors as the start block.  S not positive
+    definite: ChaseHipError whose code (and .pivot) is the index of the first non-positive pivot."""
 
-    def __init__(self, ctx, H, S, nev, nex):
+    def __init__(self, ctx, H, S, nev, nex, itype=1):
         assert H.ndim == 2 and H.shape[0] == H.shape[1] and S.shape == H.shape
-        self.ctx = ctx
+        if itype not in (1, 2, 3):
+            raise ValueError("itype must be 1, 2 or 3")
+        self.ctx, self.itype = ctx, itype
         self.cplx = bool(np.iscomplexobj(H) or np.iscomplexobj(S))
         self.N, self.nev, self.nex = H.shape[0], nev, nex
         self.H, self.S = H, S                              # the originals, for gev_residuals()
         self.dC, self.dU = ctx.array(H.astype(self._dt(), copy=False)), ctx.array(S.astype(self._dt(), copy=False))
         self.solver = None
-        info = ctx.gev_reduce(self.N, self.dC.ptr, self.N, self.dU.ptr, self.N, self.cplx)
+        if itype == 1:
+            info = ctx.gev_reduce(self.N, self.dC.ptr, self.N, self.dU.ptr, self.N, self.cplx)
+        else:
+            info = ctx.gev_reduce_itype(itype, 1, self.N, self.dC.ptr, self.N, self.dU.ptr, self.N, self.cplx)
         if info > 0:
             self.close()
-            err = ChaseHipError(info, "gev_reduce", f"S is not positive definite: pivot {info} is not positive")
-            err.pivot = info
-            raise err
+            raise self._pivot_error(info)
         self.solver = Solver(ctx, None, nev, nex, h_on_device_ptr=self.dC.ptr, N=self.N, cplx=self.cplx)
+
+    @staticmethod
+    def _pivot_error(info):
+        err = ChaseHipError(info, "gev_reduce", f"S is not positive definite: pivot {info} is not positive")
+        err.pivot = info
+        return err
 
     def _dt(self):
         return np.complex128 if self.cplx else np.float64
@@ -785,17 +823,55 @@ class GevSolver:
         """U in the upper triangle (below it: what S held)"""
         return self.dU.download()
 
+    def start_vectors(self):
+        """the start block (N x (nev + nex)) the next solve() reads when approx is set: after a solve the solver's vectors, after
+        update(H, S) their start transform with the new factor"""
+        return self.solver.V.copy(order="F")
+
+    def update(self, H, S=None):
+        """The next pencil of a sequence; the next solve() starts from the previous vectors (approx = 1, ritzv kept).
+        S given: all nev + nex columns of the block are back-transformed with the old factor, S and H are uploaded and reduced,
+        and the block is start-transformed with the new factor - all on the device.  S = None: the overlap matrix did not change;
+        only H is uploaded and reduced with the stored factor (no Cholesky), and the block stays as it is."""
+        assert H.shape == (self.N, self.N) and bool(np.iscomplexobj(H)) <= self.cplx
+        n, nc, dt = self.N, self.nev + self.nex, self._dt()
+        if S is None:
+            self.dC.upload(np.asfortranarray(H.astype(dt, copy=False)))
+            self.ctx.gev_reduce_itype(self.itype, 0, n, self.dC.ptr, n, self.dU.ptr, n, self.cplx)
+        else:
+            assert S.shape == H.shape and bool(np.iscomplexobj(S)) <= self.cplx
+            dX = self.ctx.array(self.solver.V)
+            try:
+                self.ctx.gev_backtransform_itype(self.itype, n, nc, self.dU.ptr, n, dX.ptr, n, self.cplx)
+                self.dU.upload(np.asfortranarray(S.astype(dt, copy=False)))
+                self.dC.upload(np.asfortranarray(H.astype(dt, copy=False)))
+                info = self.ctx.gev_reduce_itype(self.itype, 1, n, self.dC.ptr, n, self.dU.ptr, n, self.cplx)
+                if info > 0:
+                    raise self._pivot_error(info)
+                self.ctx.gev_starttransform(self.itype, n, nc, self.dU.ptr, n, dX.ptr, n, self.cplx)
+                self.solver.V[...] = dX.download()
+            finally:
+                dX.free()
+            self.S = S
+        self.H = H
+        self.solver.set(approx=1)
+
     def eigenpairs(self):
-        """(lambda[:nev], X[:, :nev]) with H X = S X diag(lambda), X^H S X = I"""
+        """(lambda[:nev], X[:, :nev]): itype 1, H X = S X diag(lambda) and X^H S X = I; itype 2, H S X = X diag(lambda) and
+        X^H S X = I; itype 3, S H X = X diag(lambda) and X^H S^{-1} X = I"""
         dX = self.ctx.array(self.solver.V[:, :self.nev])
-        self.ctx.gev_backtransform(self.N, self.nev, self.dU.ptr, self.N, dX.ptr, self.N, self.cplx)
+        if self.itype == 1:
+            self.ctx.gev_backtransform(self.N, self.nev, self.dU.ptr, self.N, dX.ptr, self.N, self.cplx)
+        else:
+            self.ctx.gev_backtransform_itype(self.itype, self.N, self.nev, self.dU.ptr, self.N, dX.ptr, self.N, self.cplx)
         X = dX.download()
         dX.free()
         return self.solver.ritzv[:self.nev].copy(), X
 
     def gev_residuals(self):
-        """|| H x_j - lambda_j S x_j ||_2, j < nev, from fresh four-multiplication products (phase 3) with the ORIGINAL H and S,
-        which are uploaded again for this (two more N^2 blocks while it runs)"""
+        """|| H x_j - lambda_j S x_j ||_2 (itype 1), || H S x_j - lambda_j x_j ||_2 (itype 2) or || S H x_j - lambda_j x_j ||_2
+        (itype 3), j < nev, from fresh four-multiplication products (phase 3) with the ORIGINAL H and S, which are uploaded
+        again for this (two more N^2 blocks while it runs)"""
         lam, X = self.eigenpairs()
         n, k, dt = self.N, self.nev, self._dt()
         full = lambda A: np.triu(A) + np.triu(A, 1).conj().T          # the triangle the reduction read
@@ -804,9 +880,16 @@ class GevSolver:
         out = np.zeros(k)
         try:
             check(lib.chase_hip_ctx_set_phase(self.ctx.h, 3), "set_phase")
-            self.ctx.gemm("N", n, k, n, 1.0, dH.ptr, n, dX.ptr, n, 0.0, dW.ptr, n, self.cplx)
-            self.ctx.gemm("N", n, k, n, 1.0, dS.ptr, n, dX.ptr, n, 0.0, dV.ptr, n, self.cplx)
-            check(lib.chase_hip_resid_norms(self.ctx.h, int(self.cplx), n, k, dW.ptr, n, dV.ptr, n, lam.ctypes.data,
+            if self.itype == 1:
+                self.ctx.gemm("N", n, k, n, 1.0, dH.ptr, n, dX.ptr, n, 0.0, dW.ptr, n, self.cplx)
+                self.ctx.gemm("N", n, k, n, 1.0, dS.ptr, n, dX.ptr, n, 0.0, dV.ptr, n, self.cplx)
+                rhs = dV
+            else:
+                first, second = (dS, dH) if self.itype == 2 else (dH, dS)
+                self.ctx.gemm("N", n, k, n, 1.0, first.ptr, n, dX.ptr, n, 0.0, dV.ptr, n, self.cplx)
+                self.ctx.gemm("N", n, k, n, 1.0, second.ptr, n, dV.ptr, n, 0.0, dW.ptr, n, self.cplx)
+                rhs = dX
+            check(lib.chase_hip_resid_norms(self.ctx.h, int(self.cplx), n, k, dW.ptr, n, rhs.ptr, n, lam.ctypes.data,
                                             out.ctypes.data, 0), "resid_norms")
         finally:
             lib.chase_hip_ctx_set_phase(self.ctx.h, 0)

@@ -1,10 +1,12 @@
 // capi_gev.hip — C ABI entry points of the generalized Hermitian-definite problem H x = lambda S x on one GPU
 // (include/chase_hip.h): the left triangular solve, the two-level Cholesky that leaves the strictly lower triangle alone, the
 // two-sided reduction C = U^{-H} H U^{-1} and the back-transformation X = U^{-1} Y.  They replace the three ScaLAPACK calls
-// (ppotrf, phegst, ptrtrs) the reference's docs/example/gev.rst puts around chase::Solve.
+// (ppotrf, phegst, ptrtrs) the reference's docs/example/gev.rst puts around chase::Solve.  For sequences of pencils and LAPACK's
+// problem types 2 and 3: the triangular product X <- op(U) X, C = U H U^H, the itype-aware reduction and back-transformation and
+// the start transform that makes the previous pencil's eigenvectors the start block of the next reduced problem.
 //
-// Every O(n^3) flop goes through the context's MFMA GEMM; the scalar cores are potf2_trtri / trtri_diag (factor_kernels.hip)
-// and hegs2_diag (gev_kernels.hip).  The context's phase is 0 while these run: complex products take four multiplications,
+// Every O(n^3) flop goes through the context's MFMA GEMM; the cores are potf2_trtri / trtri_diag (factor_kernels.hip), hegs2_diag
+// and the 64-row MFMA step of the triangular product, trmm_diag (gev_kernels.hip).  The context's phase is 0 while these run: complex products take four multiplications,
 // which is what the componentwise bounds of tests/gev_refs.py assume.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -100,6 +102,50 @@ int trsm_left(chase_hip_ctx* c, int cplx, char op, int n, int nrhs, const double
                     RCCHK(gemm(c, cplx, 'N', above, nrhs, nb, -1.0, R + ((long)j0 * ldr + J0) * e, ldr, P, nb, 1.0,
                                B + (long)J0 * e, ldb));
             }
+        }
+    }
+    return 0;
+}
+
+// X (n x ncols) <- op(U) X in place, U upper triangular: the mirror image of trsm_left.  Blocks of SOLVE_WB rows, op 'N' from
+// the top down and op 'C' from the bottom up, so that the rows a block needs from outside itself are still the old ones.
+// Inside a block 64-row steps X_j <- op(U_jj) X_j (trmm_diag: the triangle in LDS, f64 MFMA, in place - no panel buffer and no
+// copy back), each followed by the rectangle inside the block; then ONE product with a long inner dimension for everything
+// outside the block.
+int trmm_left(chase_hip_ctx* c, int cplx, char op, int n, int ncols, const double* U, long ldu, double* X, long ldx)
+{
+    if (n <= 0 || ncols <= 0) return 0;
+    const int e = ept_of(cplx);
+    if (op == 'N') {
+        for (int J0 = 0; J0 < n; J0 += SOLVE_WB) {
+            const int Jend = imin(n, J0 + SOLVE_WB), wb = Jend - J0;
+            for (int j0 = J0; j0 < Jend; j0 += NB) {
+                const int nb = imin(NB, Jend - j0);
+                double* Xj = X + (long)j0 * e;
+                KCHK(trmm_diag(c->stream, cplx != 0, false, U + ((long)j0 * ldu + j0) * e, ldu, Xj, ldx, nb, ncols), "trmm_diag");
+                const int rest = Jend - j0 - nb;               // X_j += U[j, j0+nb : Jend] X[j0+nb : Jend], rows not yet overwritten
+                if (rest > 0)
+                    RCCHK(gemm(c, cplx, 'N', nb, ncols, rest, 1.0, U + ((long)(j0 + nb) * ldu + j0) * e, ldu,
+                               X + (long)(j0 + nb) * e, ldx, 1.0, Xj, ldx));
+            }
+            if (Jend < n)        // X_J += U[J, Jend:n] X[Jend:n, :]
+                RCCHK(gemm(c, cplx, 'N', wb, ncols, n - Jend, 1.0, U + ((long)Jend * ldu + J0) * e, ldu, X + (long)Jend * e, ldx, 1.0,
+                           X + (long)J0 * e, ldx));
+        }
+    } else {
+        for (int J0 = (n - 1) / SOLVE_WB * SOLVE_WB; J0 >= 0; J0 -= SOLVE_WB) {
+            const int Jend = imin(n, J0 + SOLVE_WB), wb = Jend - J0;
+            for (int j0 = J0 + (wb - 1) / NB * NB; j0 >= J0; j0 -= NB) {
+                const int nb = imin(NB, Jend - j0);
+                double* Xj = X + (long)j0 * e;
+                KCHK(trmm_diag(c->stream, cplx != 0, true, U + ((long)j0 * ldu + j0) * e, ldu, Xj, ldx, nb, ncols), "trmm_diag");
+                const int above = j0 - J0;                     // X_j += U[J0 : j0, j]^H X[J0 : j0], rows not yet overwritten
+                if (above > 0)
+                    RCCHK(gemm(c, cplx, 'C', nb, ncols, above, 1.0, U + ((long)j0 * ldu + J0) * e, ldu, X + (long)J0 * e, ldx, 1.0,
+                               Xj, ldx));
+            }
+            if (J0 > 0)          // X_J += U[0:J0, J]^H X[0:J0, :]
+                RCCHK(gemm(c, cplx, 'C', wb, ncols, J0, 1.0, U + (long)J0 * ldu * e, ldu, X, ldx, 1.0, X + (long)J0 * e, ldx));
         }
     }
     return 0;
@@ -269,6 +315,96 @@ int chase_hip_gev_backtransform(chase_hip_ctx* c, int cplx, int n, int ncols, co
     if (!U || !X) return set_error(CHASE_HIP_EINVAL, "gev_backtransform: NULL matrix");
     phase_zero pz(c);
     return trsm_left(c, cplx, 'N', n, ncols, (const double*)U, ldu, (double*)X, ldx);
+}
+
+/* X (n x ncols, device) <- op(U) X in place, U upper triangular n x n (device), op 'N' or 'C' (real data: 'C' is the transpose).
+ * The diagonal is used as stored; the strictly lower triangle of U is never read; rows beyond n are untouched. */
+int chase_hip_trmm_left_upper(chase_hip_ctx* c, int cplx, char op, int n, int ncols, const void* U, long ldu, void* X, long ldx)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "trmm_left_upper: NULL ctx");
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    if (c->oplog_on) c->oplog_add("trmm_left_upper", n, ncols, op, 0);
+    if (op == 'n') op = 'N';
+    if (op == 'c') op = 'C';
+    if (op != 'N' && op != 'C') return set_error(CHASE_HIP_EINVAL, "trmm_left_upper: op must be 'N' or 'C'");
+    if (n < 0 || ncols < 0 || ldu < n || ldx < n) return set_error(CHASE_HIP_EINVAL, "trmm_left_upper: bad shape");
+    if (n == 0 || ncols == 0) return 0;
+    if (!U || !X) return set_error(CHASE_HIP_EINVAL, "trmm_left_upper: NULL matrix");
+    phase_zero pz(c);
+    return trmm_left(c, cplx, op, n, ncols, (const double*)U, ldu, (double*)X, ldx);
+}
+
+/* A <- U A U^H (LAPACK xHEGST, itype 2 / 3, uplo 'U') with the argument and result contract of chase_hip_hegst_upper: two left
+ * products on the completed matrix with an in-place conjugate transpose between them, U (U A)^H = U A U^H for Hermitian A;
+ * the lower triangle of the result is kept and mirrored. */
+int chase_hip_hegst_product_upper(chase_hip_ctx* c, int cplx, int n, void* A, long lda, const void* U, long ldu)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "hegst_product_upper: NULL ctx");
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    if (c->oplog_on) c->oplog_add("hegst_product_upper", n, 0, 0, 0);
+    if (n < 0 || lda < n || ldu < n) return set_error(CHASE_HIP_EINVAL, "hegst_product_upper: bad shape");
+    if (n == 0) return 0;
+    if (!A || !U) return set_error(CHASE_HIP_EINVAL, "hegst_product_upper: NULL matrix");
+    phase_zero pz(c);
+    const int e = ept_of(cplx);
+    KCHK(mirror_upper(c->stream, (double*)A, lda, n, e), "mirror_upper");
+    RCCHK(trmm_left(c, cplx, 'N', n, n, (const double*)U, ldu, (double*)A, lda));
+    KCHK(conj_transpose_inplace(c->stream, cplx != 0, (double*)A, lda, n), "conj_transpose_inplace");
+    RCCHK(trmm_left(c, cplx, 'N', n, n, (const double*)U, ldu, (double*)A, lda));
+    KCHK(mirror_lower(c->stream, (double*)A, lda, n, e, 1), "mirror_lower");
+    return 0;
+}
+
+/* gev_reduce for the three LAPACK problem types: itype 1, H x = lambda S x, A <- U^{-H} A U^{-1}; itype 2, H S x = lambda x, and
+ * itype 3, S H x = lambda x, A <- U A U^H.  factor = 1: S <- U first, as gev_reduce does (itype 1, factor 1 IS gev_reduce);
+ * factor = 0: S already holds U from an earlier call and only the two-sided step runs. */
+int chase_hip_gev_reduce_itype(chase_hip_ctx* c, int cplx, int itype, int factor, int n, void* A, long lda, void* S, long lds_)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "gev_reduce_itype: NULL ctx");
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    if (c->oplog_on) c->oplog_add("gev_reduce_itype", n, itype, 0, factor);
+    if (itype < 1 || itype > 3) return set_error(CHASE_HIP_EINVAL, "gev_reduce_itype: itype must be 1, 2 or 3");
+    if (factor != 0 && factor != 1) return set_error(CHASE_HIP_EINVAL, "gev_reduce_itype: factor must be 0 or 1");
+    if (n < 0 || lda < n || lds_ < n) return set_error(CHASE_HIP_EINVAL, "gev_reduce_itype: bad shape");
+    if (n == 0) return 0;
+    if (!A || !S) return set_error(CHASE_HIP_EINVAL, "gev_reduce_itype: NULL matrix");
+    if (factor) {
+        const int info = chase_hip_potrf_upper_blocked(c, cplx, n, S, lds_, 0);
+        if (info != 0) return info;
+    }
+    return itype == 1 ? chase_hip_hegst_upper(c, cplx, n, A, lda, S, lds_, 0) : chase_hip_hegst_product_upper(c, cplx, n, A, lda, S, lds_);
+}
+
+/* X (n x ncols) <- U^{-1} X (itype 1 and 2) or U^H X (itype 3): eigenvectors of the reduced problem to those of the pencil */
+int chase_hip_gev_backtransform_itype(chase_hip_ctx* c, int cplx, int itype, int n, int ncols, const void* U, long ldu, void* X,
+                                      long ldx)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "gev_backtransform_itype: NULL ctx");
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    if (c->oplog_on) c->oplog_add("gev_backtransform_itype", n, ncols, 0, itype);
+    if (itype < 1 || itype > 3) return set_error(CHASE_HIP_EINVAL, "gev_backtransform_itype: itype must be 1, 2 or 3");
+    if (n < 0 || ncols < 0 || ldu < n || ldx < n) return set_error(CHASE_HIP_EINVAL, "gev_backtransform_itype: bad shape");
+    if (n == 0 || ncols == 0) return 0;
+    if (!U || !X) return set_error(CHASE_HIP_EINVAL, "gev_backtransform_itype: NULL matrix");
+    phase_zero pz(c);
+    return itype == 3 ? trmm_left(c, cplx, 'C', n, ncols, (const double*)U, ldu, (double*)X, ldx)
+                      : trsm_left(c, cplx, 'N', n, ncols, (const double*)U, ldu, (double*)X, ldx);
+}
+
+/* The inverse of gev_backtransform_itype, X (n x ncols) <- U X (itype 1 and 2) or U^{-H} X (itype 3): approximate eigenvectors
+ * of the pencil become a start block of the reduced problem */
+int chase_hip_gev_starttransform(chase_hip_ctx* c, int cplx, int itype, int n, int ncols, const void* U, long ldu, void* X, long ldx)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "gev_starttransform: NULL ctx");
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    if (c->oplog_on) c->oplog_add("gev_starttransform", n, ncols, 0, itype);
+    if (itype < 1 || itype > 3) return set_error(CHASE_HIP_EINVAL, "gev_starttransform: itype must be 1, 2 or 3");
+    if (n < 0 || ncols < 0 || ldu < n || ldx < n) return set_error(CHASE_HIP_EINVAL, "gev_starttransform: bad shape");
+    if (n == 0 || ncols == 0) return 0;
+    if (!U || !X) return set_error(CHASE_HIP_EINVAL, "gev_starttransform: NULL matrix");
+    phase_zero pz(c);
+    return itype == 3 ? trsm_left(c, cplx, 'C', n, ncols, (const double*)U, ldu, (double*)X, ldx)
+                      : trmm_left(c, cplx, 'N', n, ncols, (const double*)U, ldu, (double*)X, ldx);
 }
 
 } // extern "C"

@@ -1,6 +1,7 @@
 // gev_kernels.hip — the scalar cores of the reduction H x = lambda S x -> C y = lambda y with S = U^H U, C = U^{-H} H U^{-1}
-// (capi_gev.hip): the LDS-resident two-sided reduction of one diagonal block and the triangle-only copies the blocked
-// drivers need so that a strictly lower triangle is neither read nor written.
+// (capi_gev.hip): the LDS-resident two-sided reduction of one diagonal block, the triangle-only copies the blocked drivers
+// need so that a strictly lower triangle is neither read nor written, and - for sequences and itype 2 / 3 - the MFMA diagonal
+// step of the triangular product X <- op(U) X (trmm_diag) and the in-place conjugate transpose.
 //
 // Reference call site replaced: the p?hegst of docs/example/gev.rst (LAPACK xHEGS2, itype = 1, uplo = 'U', for one block).
 //
@@ -105,6 +106,158 @@ int hegs2_diag(hipStream_t st, bool cplx, double* A, long lda, const double* U, 
     if (nb > GNB) return (int)hipErrorInvalidValue;
     if (cplx) hipLaunchKernelGGL(hegs2_diag_kernel<true>, dim3(1), dim3(256), 0, st, A, lda, U, ldu, nb);
     else      hipLaunchKernelGGL(hegs2_diag_kernel<false>, dim3(1), dim3(256), 0, st, A, lda, U, ldu, nb);
+    return (int)hipGetLastError();
+}
+
+// ---- trmm_diag: X_j <- op(U_jj) X_j for one 64-row step of chase_hip_trmm_left_upper ------------------------------------------------
+// One 256-thread workgroup per 64-column tile of X; wave w owns the tile's columns 16 w ... 16 w + 15 and all four 16-row groups
+// of the result, so the triangle's uneven work per row group is the same for every wave.  Both operands live in LDS on split
+// planes (real, imaginary): the upper triangle of U_jj as stored - everything below the diagonal and beyond nb is BUILT as zeros,
+// never read, and for op C the imaginary plane is negated while staging - and the X tile, rows beyond nb zero.  The product runs
+// on v_mfma_f64_16x16x4_f64 with the roles swapped as in gemm_mfma_f64.hip (first operand the X fragment, second the U fragment),
+// so that the accumulator's lanes run along the rows of the result and a 16-lane group stores 128 (complex 256) contiguous
+// bytes.  k-blocks of 4 that lie wholly on the zero side of the diagonal of a 16-row group are skipped.  Complex: four real
+// products, Re = Ur Xr - Ui Xi, Im = Ur Xi + Ui Xr.
+//
+// LDS layout: consecutive lanes on consecutive doubles everywhere.  Staging: lane i writes row i of a column (ds_write_b64, 16
+// lanes = 32 banks).  Fragment reads are ds_read_b64 in two groups of 32 lanes = 16 values of the non-k index x 2 values of k
+// on 64 banks, so the 32 doubles must fall on distinct double-slots mod 32:
+//   X[k, col]       at k + 66 col  ->  2 col + k          (ld 66 = 2 mod 32)
+//   op N: U[i, k]   at i + 80 k    ->  i + 16 k           (ld 80 = 16 mod 32)
+//   op C: U[k, i]^* at k + 66 i    ->  2 i + k            (ld 66; the block is stored as it lies and read across)
+// No operand is read at a stride that is a multiple of the bank width; the transposed copy hegs2_diag keeps is not needed.
+namespace {
+typedef double gd4 __attribute__((ext_vector_type(4)));
+constexpr int TLX = 66;
+}
+
+template <bool CPLX, bool OPC>
+__global__ __launch_bounds__(256) void trmm_diag_kernel(const double* __restrict__ U, long ldu, double* __restrict__ X, long ldx,
+                                                        int nb, int ncols)
+{
+    constexpr int LU = OPC ? 66 : 80, NP = CPLX ? 2 : 1, EPT = CPLX ? 2 : 1;
+    __shared__ double Us[NP * LU * GNB];
+    __shared__ double Xs[NP * TLX * GNB];
+    double* const Ui = Us + (CPLX ? LU * GNB : 0);
+    double* const Xi = Xs + (CPLX ? TLX * GNB : 0);
+    const int tid = threadIdx.x;
+    const int li = tid & 63, lj = tid >> 6;
+    const int c0 = blockIdx.x * GNB;
+    const int cw = ncols - c0 < GNB ? ncols - c0 : GNB;
+
+    for (int j = lj; j < GNB; j += 4) {
+        double ur = 0.0, ui = 0.0, xr = 0.0, xi = 0.0;
+        if (li <= j && j < nb) {
+            const double* u = U + ((long)j * ldu + li) * EPT;
+            ur = u[0];
+            if (CPLX) ui = OPC ? -u[1] : u[1];
+        }
+        if (li < nb && j < cw) {
+            const double* x = X + ((long)(c0 + j) * ldx + li) * EPT;
+            xr = x[0];
+            if (CPLX) xi = x[1];
+        }
+        Us[li + j * LU] = ur;
+        Xs[li + j * TLX] = xr;
+        if (CPLX) { Ui[li + j * LU] = ui; Xi[li + j * TLX] = xi; }
+    }
+    __syncthreads();
+
+    const int w = tid >> 6, lr = tid & 15, lk = (tid & 63) >> 4;
+    gd4 acc[4][NP];
+    #pragma unroll
+    for (int ib = 0; ib < 4; ++ib)
+        #pragma unroll
+        for (int p = 0; p < NP; ++p) acc[ib][p] = gd4{0.0, 0.0, 0.0, 0.0};
+    const int kend = (nb + 3) >> 2;
+    const int xo = TLX * (16 * w + lr);
+    for (int k4 = 0; k4 < kend; ++k4) {
+        const int k = 4 * k4 + lk;
+        const double xr = Xs[k + xo];
+        double xi = 0.0, nxi = 0.0;
+        if (CPLX) { xi = Xi[k + xo]; nxi = -xi; }
+        #pragma unroll
+        for (int ib = 0; ib < 4; ++ib) {
+            // rows 16 ib ... 16 ib + 15 of op(U): op N is zero for k < 16 ib, op C for k >= 16 (ib + 1); rows beyond nb are not stored
+            const bool live = (16 * ib < nb) && (OPC ? k4 < 4 * (ib + 1) : k4 >= 4 * ib);
+            if (!live) continue;
+            const int uo = OPC ? k + LU * (16 * ib + lr) : (16 * ib + lr) + LU * k;
+            const double ur = Us[uo];
+            if (CPLX) {
+                const double ui = Ui[uo];
+                acc[ib][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(xr, ur, acc[ib][0], 0, 0, 0);
+                acc[ib][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(nxi, ui, acc[ib][0], 0, 0, 0);
+                acc[ib][NP - 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(xi, ur, acc[ib][NP - 1], 0, 0, 0);
+                acc[ib][NP - 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(xr, ui, acc[ib][NP - 1], 0, 0, 0);
+            } else {
+                acc[ib][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(xr, ur, acc[ib][0], 0, 0, 0);
+            }
+        }
+    }
+
+    // accumulator register r of lane (lr, lk): row 16 ib + lr of the result, column 16 w + lk + 4 r of the tile.  Every read of
+    // the tile happened before the barrier above, so the result goes over it in place.
+    #pragma unroll
+    for (int ib = 0; ib < 4; ++ib) {
+        const int row = 16 * ib + lr;
+        #pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int col = 16 * w + lk + 4 * r;
+            if (row < nb && col < cw) {
+                double* x = X + ((long)(c0 + col) * ldx + row) * EPT;
+                if (CPLX) { double2 v; v.x = acc[ib][0][r]; v.y = acc[ib][NP - 1][r]; *(double2*)x = v; }
+                else x[0] = acc[ib][0][r];
+            }
+        }
+    }
+}
+
+int trmm_diag(hipStream_t st, bool cplx, bool op_c, const double* U, long ldu, double* X, long ldx, int nb, int ncols)
+{
+    if (nb <= 0 || ncols <= 0) return 0;
+    if (nb > GNB) return (int)hipErrorInvalidValue;
+    const dim3 grid((ncols + GNB - 1) / GNB), block(256);
+    if (cplx) {
+        if (op_c) hipLaunchKernelGGL((trmm_diag_kernel<true, true>), grid, block, 0, st, U, ldu, X, ldx, nb, ncols);
+        else      hipLaunchKernelGGL((trmm_diag_kernel<true, false>), grid, block, 0, st, U, ldu, X, ldx, nb, ncols);
+    } else {
+        if (op_c) hipLaunchKernelGGL((trmm_diag_kernel<false, true>), grid, block, 0, st, U, ldu, X, ldx, nb, ncols);
+        else      hipLaunchKernelGGL((trmm_diag_kernel<false, false>), grid, block, 0, st, U, ldu, X, ldx, nb, ncols);
+    }
+    return (int)hipGetLastError();
+}
+
+// A <- A^H in place (n x n): one workgroup per pair of 32 x 32 tiles (bi <= bj), both staged in LDS (ld 33) and written to each
+// other's place conjugated, so reads and writes both run down columns.
+template <bool CPLX>
+__global__ __launch_bounds__(256) void conj_transpose_kernel(double* __restrict__ A, long lda, int n)
+{
+    using E = typename std::conditional<CPLX, gcd, double>::type;
+    constexpr int T = 32, LT = T + 1;
+    __shared__ E t1[T * LT];
+    __shared__ E t2[T * LT];
+    const int bi = blockIdx.x, bj = blockIdx.y;
+    if (bi > bj) return;
+    E* Ag = (E*)A;
+    const int r0 = bi * T, c0 = bj * T;
+    const int li = threadIdx.x & 31, lj = threadIdx.x >> 5;
+    for (int j = lj; j < T; j += 8) {
+        if (r0 + li < n && c0 + j < n) t1[li + j * LT] = Ag[(long)(c0 + j) * lda + r0 + li];              // t1[a, b] = A[r0 + a, c0 + b]
+        if (bi != bj && c0 + li < n && r0 + j < n) t2[li + j * LT] = Ag[(long)(r0 + j) * lda + c0 + li];  // t2[a, b] = A[c0 + a, r0 + b]
+    }
+    __syncthreads();
+    for (int j = lj; j < T; j += 8) {
+        if (r0 + li < n && c0 + j < n) Ag[(long)(c0 + j) * lda + r0 + li] = g_conj(bi == bj ? t1[j + li * LT] : t2[j + li * LT]);
+        if (bi != bj && c0 + li < n && r0 + j < n) Ag[(long)(r0 + j) * lda + c0 + li] = g_conj(t1[j + li * LT]);
+    }
+}
+
+int conj_transpose_inplace(hipStream_t st, bool cplx, double* A, long lda, int n)
+{
+    if (n <= 0) return 0;
+    const int nt = (n + 31) / 32;
+    if (cplx) hipLaunchKernelGGL(conj_transpose_kernel<true>, dim3(nt, nt), dim3(256), 0, st, A, lda, n);
+    else      hipLaunchKernelGGL(conj_transpose_kernel<false>, dim3(nt, nt), dim3(256), 0, st, A, lda, n);
     return (int)hipGetLastError();
 }
 

@@ -142,5 +142,10 @@ int hegs2_diag(hipStream_t st, bool cplx, double* A, long lda, const double* U, 
 // dst[i, j] = src[i, j] / dst[i, j] += src[i, j] for i <= j < n (leading dimensions in elements, ept doubles per element)
 int copy_upper(hipStream_t st, const double* src, long ld_src, double* dst, long ld_dst, int n, int ept);
 int add_upper(hipStream_t st, const double* src, long ld_src, double* dst, long ld_dst, int n, int ept);
+// X (nb x ncols, nb <= 64) <- op(U) X in place, U the upper triangle of an nb x nb block (nothing below its diagonal is read),
+// op_c: op = conjugate transpose; one workgroup per 64 columns, f64 MFMA, four multiplications per complex product
+int trmm_diag(hipStream_t st, bool cplx, bool op_c, const double* U, long ldu, double* X, long ldx, int nb, int ncols);
+// A (n x n) <- A^H in place
+int conj_transpose_inplace(hipStream_t st, bool cplx, double* A, long lda, int n);
 
 } // namespace chase_hip

@@ -2,7 +2,9 @@
 // ?chase_gev_reduce_ and ?chase_gev_backtransform_ are the ppotrf + phegst and the ptrtrs that the reference's
 // docs/example/gev.rst puts around chase::Solve.  Host pointers in, results in place; the matrices are moved to the device,
 // worked on by capi_gev.hip and moved back.  The intended sequence: reduce -> ?chase_init_ / ?chase_ / ?chase_finalize_ on the
-// reduced H -> backtransform of the eigenvectors with the U that reduce left in S.
+// reduced H -> backtransform of the eigenvectors with the U that reduce left in S.  The _itype forms and ?chase_gev_starttransform_
+// add LAPACK's problem types 2 and 3 and the warm step of a sequence (mode 'A'): reduce_itype -> starttransform of the previous
+// block -> ?chase_ -> backtransform_itype.
 #include <cstdlib>
 #include "../../include/chase_c_interface.h"
 #include "../../include/chase_hip.h"
@@ -31,10 +33,12 @@ struct DevMat {                                   // an m x n device copy of a h
     int down(int cplx, int m, int n, void* host, int ldh) { return chase_hip_download_matrix(c, cplx, m, n, p, m, host, ldh); }
 };
 
-void reduce(int cplx, int N, void* H, int ldh, void* S, int lds, int* info)
+// itype 0: the plain entry point (chase_hip_gev_reduce)
+void reduce(int cplx, int itype, int factor, int N, void* H, int ldh, void* S, int lds, int* info)
 {
     if (!info) return;
     *info = CHASE_HIP_EINVAL;
+    if (itype < 0 || itype > 3 || (factor != 0 && factor != 1)) return;
     if (N < 0 || ldh < N || lds < N || (N > 0 && (!H || !S))) return;
     *info = 0;
     if (N == 0) return;
@@ -42,17 +46,20 @@ void reduce(int cplx, int N, void* H, int ldh, void* S, int lds, int* info)
     DevMat dH(g_gev_ctx), dS(g_gev_ctx);
     int rc = dH.up(cplx, N, N, H, ldh);
     if (!rc) rc = dS.up(cplx, N, N, S, lds);
-    if (!rc) rc = chase_hip_gev_reduce(g_gev_ctx, cplx, N, dH.p, N, dS.p, N);
+    if (!rc) rc = itype == 0 ? chase_hip_gev_reduce(g_gev_ctx, cplx, N, dH.p, N, dS.p, N)
+                             : chase_hip_gev_reduce_itype(g_gev_ctx, cplx, itype, factor, N, dH.p, N, dS.p, N);
     if (rc) { *info = rc; return; }               // S not positive definite (rc > 0) or a runtime error: H and S as they were
     rc = dH.down(cplx, N, N, H, ldh);
-    if (!rc) rc = dS.down(cplx, N, N, S, lds);    // the strictly lower triangle comes back as it went
+    if (!rc && factor) rc = dS.down(cplx, N, N, S, lds);    // the strictly lower triangle comes back as it went
     *info = rc;
 }
 
-void backtransform(int cplx, int N, int ncols, void* U, int ldu, void* V, int ldv, int* info)
+// itype 0: the plain entry point (chase_hip_gev_backtransform); start: chase_hip_gev_starttransform
+void backtransform(int cplx, int itype, bool start, int N, int ncols, void* U, int ldu, void* V, int ldv, int* info)
 {
     if (!info) return;
     *info = CHASE_HIP_EINVAL;
+    if (itype < 0 || itype > 3) return;
     if (N < 0 || ncols < 0 || ldu < N || ldv < N || (N > 0 && (!U || (ncols > 0 && !V)))) return;
     *info = 0;
     if (N == 0 || ncols == 0) return;
@@ -60,21 +67,55 @@ void backtransform(int cplx, int N, int ncols, void* U, int ldu, void* V, int ld
     DevMat dU(g_gev_ctx), dV(g_gev_ctx);
     int rc = dU.up(cplx, N, N, U, ldu);
     if (!rc) rc = dV.up(cplx, N, ncols, V, ldv);
-    if (!rc) rc = chase_hip_gev_backtransform(g_gev_ctx, cplx, N, ncols, dU.p, N, dV.p, N);
+    if (!rc) rc = start       ? chase_hip_gev_starttransform(g_gev_ctx, cplx, itype, N, ncols, dU.p, N, dV.p, N)
+                  : itype == 0 ? chase_hip_gev_backtransform(g_gev_ctx, cplx, N, ncols, dU.p, N, dV.p, N)
+                               : chase_hip_gev_backtransform_itype(g_gev_ctx, cplx, itype, N, ncols, dU.p, N, dV.p, N);
     if (!rc) rc = dV.down(cplx, N, ncols, V, ldv);
     *info = rc;
+}
+
+// the _itype entry points take itype 1 .. 3 only
+bool itype_ok(int itype, int* info)
+{
+    if (itype >= 1 && itype <= 3) return true;
+    if (info) *info = CHASE_HIP_EINVAL;
+    return false;
 }
 } // namespace
 
 extern "C" {
-void dchase_gev_reduce_(int* N, double* H, int* ldh, double* S, int* lds, int* info) { reduce(0, *N, H, *ldh, S, *lds, info); }
-void zchase_gev_reduce_(int* N, void* H, int* ldh, void* S, int* lds, int* info) { reduce(1, *N, H, *ldh, S, *lds, info); }
+void dchase_gev_reduce_(int* N, double* H, int* ldh, double* S, int* lds, int* info) { reduce(0, 0, 1, *N, H, *ldh, S, *lds, info); }
+void zchase_gev_reduce_(int* N, void* H, int* ldh, void* S, int* lds, int* info) { reduce(1, 0, 1, *N, H, *ldh, S, *lds, info); }
 void dchase_gev_backtransform_(int* N, int* ncols, double* U, int* ldu, double* V, int* ldv, int* info)
 {
-    backtransform(0, *N, *ncols, U, *ldu, V, *ldv, info);
+    backtransform(0, 0, false, *N, *ncols, U, *ldu, V, *ldv, info);
 }
 void zchase_gev_backtransform_(int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info)
 {
-    backtransform(1, *N, *ncols, U, *ldu, V, *ldv, info);
+    backtransform(1, 0, false, *N, *ncols, U, *ldu, V, *ldv, info);
+}
+void dchase_gev_reduce_itype_(int* itype, int* factor, int* N, double* H, int* ldh, double* S, int* lds, int* info)
+{
+    if (itype_ok(*itype, info)) reduce(0, *itype, *factor, *N, H, *ldh, S, *lds, info);
+}
+void zchase_gev_reduce_itype_(int* itype, int* factor, int* N, void* H, int* ldh, void* S, int* lds, int* info)
+{
+    if (itype_ok(*itype, info)) reduce(1, *itype, *factor, *N, H, *ldh, S, *lds, info);
+}
+void dchase_gev_backtransform_itype_(int* itype, int* N, int* ncols, double* U, int* ldu, double* V, int* ldv, int* info)
+{
+    if (itype_ok(*itype, info)) backtransform(0, *itype, false, *N, *ncols, U, *ldu, V, *ldv, info);
+}
+void zchase_gev_backtransform_itype_(int* itype, int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info)
+{
+    if (itype_ok(*itype, info)) backtransform(1, *itype, false, *N, *ncols, U, *ldu, V, *ldv, info);
+}
+void dchase_gev_starttransform_(int* itype, int* N, int* ncols, double* U, int* ldu, double* V, int* ldv, int* info)
+{
+    if (itype_ok(*itype, info)) backtransform(0, *itype, true, *N, *ncols, U, *ldu, V, *ldv, info);
+}
+void zchase_gev_starttransform_(int* itype, int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info)
+{
+    if (itype_ok(*itype, info)) backtransform(1, *itype, true, *N, *ncols, U, *ldu, V, *ldv, info);
 }
 }

@@ -68,12 +68,25 @@ void cchase_get_eigenpairs_(void* LEigsV, int* ld, float* ritzv);
  * (upper triangle read) becomes U^{-H} H U^{-1}, both triangles, exactly Hermitian.  backtransform: V (N x ncols) <- U^{-1} V.
  * *info: 0, the index of the first non-positive pivot of S (H and S are then unchanged), or a negative CHASE_HIP_* code.
  * Sequence: ?chase_gev_reduce_ -> ?chase_init_ / ?chase_ / ?chase_finalize_ on the reduced H -> ?chase_gev_backtransform_ on
- * the eigenvectors; the Ritz values are those of (H, S), the vectors come out S-orthonormal.  Not provided: grid solvers,
- * single precision, pseudo-Hermitian problems, itype 2 and 3, and the Y = U X that approximate start vectors would need. */
+ * the eigenvectors; the Ritz values are those of (H, S), the vectors come out S-orthonormal.
+ * The _itype forms take LAPACK's problem type: 1, H x = lambda S x; 2, H S x = lambda x; 3, S H x = lambda x (2 and 3 reduce to
+ * U H U^H).  factor = 1 factors S as reduce does; factor = 0 says S already holds U - the overlap matrix of a sequence did not
+ * change - and only H is reduced.  backtransform_itype: V <- U^{-1} V (itype 1, 2) or U^H V (itype 3).  starttransform is its
+ * inverse, V <- U V (itype 1, 2) or U^{-H} V (itype 3): it makes approximate eigenvectors of the pencil a start block of the
+ * reduced problem.  A warm step of a sequence: reduce_itype on the new pencil -> starttransform of the previous step's
+ * back-transformed block, all nev + nex columns, into V -> ?chase_ with mode 'A' and the previous ritzv -> backtransform_itype
+ * (examples/c_gev_sequence.c).  itype outside 1 .. 3 or factor outside 0 / 1: *info = CHASE_HIP_EINVAL.
+ * Not provided: grid solvers, single precision, pseudo-Hermitian pencils. */
 void dchase_gev_reduce_(int* N, double* H, int* ldh, double* S, int* lds, int* info);
 void zchase_gev_reduce_(int* N, void* H, int* ldh, void* S, int* lds, int* info);
 void dchase_gev_backtransform_(int* N, int* ncols, double* U, int* ldu, double* V, int* ldv, int* info);
 void zchase_gev_backtransform_(int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info);
+void dchase_gev_reduce_itype_(int* itype, int* factor, int* N, double* H, int* ldh, double* S, int* lds, int* info);
+void zchase_gev_reduce_itype_(int* itype, int* factor, int* N, void* H, int* ldh, void* S, int* lds, int* info);
+void dchase_gev_backtransform_itype_(int* itype, int* N, int* ncols, double* U, int* ldu, double* V, int* ldv, int* info);
+void zchase_gev_backtransform_itype_(int* itype, int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info);
+void dchase_gev_starttransform_(int* itype, int* N, int* ncols, double* U, int* ldu, double* V, int* ldv, int* info);
+void zchase_gev_starttransform_(int* itype, int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info);
 void chase_enable_sym_check_(int* flag);    /* interface/chase_c_interface.cpp:4055: flag kept for callers that set it */
 /* unified configuration setters and build queries (interface/chase_c_interface.h:207-238): act on the live solver instance
  * (sequential or distributed), silent when none is initialised */

@@ -406,6 +406,29 @@ int chase_hip_hegst_upper(chase_hip_ctx* ctx, int cplx, int n, void* A, long lda
 int chase_hip_gev_reduce(chase_hip_ctx* ctx, int cplx, int n, void* A, long lda, void* S, long lds);
 /* X (n x ncols) <- U^{-1} X: the eigenvectors of the reduced problem become those of (H, S), S-orthonormal */
 int chase_hip_gev_backtransform(chase_hip_ctx* ctx, int cplx, int n, int ncols, const void* U, long ldu, void* X, long ldx);
+/* X (n x ncols) <- op(U) X in place, U upper triangular, op 'N' or 'C' (real data: the transpose).  The diagonal is used as
+ * stored; the strictly lower triangle of U is never read; empty operands are legal.  The mirror image of trsm_left_upper: blocks
+ * of 256 rows, op N from the top down and op C from the bottom up; inside a block 64-row steps through trmm_diag (the triangle
+ * and the tile of X in LDS, f64 MFMA, written over the tile in place), then one long product for the rows outside the block. */
+int chase_hip_trmm_left_upper(chase_hip_ctx* ctx, int cplx, char op, int n, int ncols, const void* U, long ldu, void* X, long ldx);
+/* A <- U A U^H (LAPACK xHEGST, itype 2 and 3, uplo 'U') with the contract of chase_hip_hegst_upper: A is read from its upper
+ * triangle only, U likewise; on return both triangles of A hold the result, the lower one the bitwise conjugate of the upper
+ * one, the imaginary diagonal +0.  Two left products on the completed matrix with an in-place conjugate transpose between them
+ * (U (U A)^H = U A U^H), one triangle kept and mirrored: n^3 multiply-adds. */
+int chase_hip_hegst_product_upper(chase_hip_ctx* ctx, int cplx, int n, void* A, long lda, const void* U, long ldu);
+/* gev_reduce for LAPACK's three problem types.  itype 1: H x = lambda S x, A <- U^{-H} A U^{-1}.  itype 2: H S x = lambda x, and
+ * itype 3: S H x = lambda x, A <- U A U^H.  factor = 1: S <- U first (itype 1, factor 1 is chase_hip_gev_reduce bit for bit;
+ * info > 0 and A untouched when S is not positive definite).  factor = 0: S already holds U from an earlier call - the overlap
+ * matrix of a sequence did not change - and only the two-sided step runs.  Any other itype or factor: CHASE_HIP_EINVAL. */
+int chase_hip_gev_reduce_itype(chase_hip_ctx* ctx, int cplx, int itype, int factor, int n, void* A, long lda, void* S, long lds);
+/* X (n x ncols) <- U^{-1} X for itype 1 and 2, X <- U^H X for itype 3: eigenvectors y of the reduced problem become those of
+ * the pencil (X^H S X = I for itype 1 and 2, X^H S^{-1} X = I for itype 3) */
+int chase_hip_gev_backtransform_itype(chase_hip_ctx* ctx, int cplx, int itype, int n, int ncols, const void* U, long ldu, void* X,
+                                      long ldx);
+/* the inverse of gev_backtransform_itype: X <- U X for itype 1 and 2, X <- U^{-H} X for itype 3.  Approximate eigenvectors of the
+ * pencil - the previous step's of a sequence - become the start block of the reduced problem (mode 'A' / approx) */
+int chase_hip_gev_starttransform(chase_hip_ctx* ctx, int cplx, int itype, int n, int ncols, const void* U, long ldu, void* X,
+                                 long ldx);
 /* variant 1 = cholQR1, 2 = cholQR2, 3 = shiftedcholQR2 (linalg/internal/cpu/cholqr1.hpp:41-189); returns info */
 int chase_hip_cholqr(chase_hip_ctx* ctx, int cplx, int m, int n, void* V, long ldv, void* A, long lda, int variant,
                      long m_global);
