@@ -103,6 +103,15 @@ _sig("chase_hip_hegst_product_upper", c_int, c_void_p, c_int, c_int, c_void_p, c
 _sig("chase_hip_gev_reduce_itype", c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
 _sig("chase_hip_gev_backtransform_itype", c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
 _sig("chase_hip_gev_starttransform", c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_gemm_s_op", c_int, *lib.chase_hip_gemm_s.argtypes)
+_sig("chase_hip_gemm_c_op", c_int, *lib.chase_hip_gemm_c.argtypes)
+_sig("chase_hip_trsm_left_upper_sp", c_int, *lib.chase_hip_trsm_left_upper.argtypes)
+_sig("chase_hip_trmm_left_upper_sp", c_int, *lib.chase_hip_trmm_left_upper.argtypes)
+_sig("chase_hip_potrf_upper_blocked_sp", c_int, *lib.chase_hip_potrf_upper_blocked.argtypes)
+_sig("chase_hip_hegst_upper_sp", c_int, c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_gev_reduce_sp", c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_long)
+_sig("chase_hip_gev_backtransform_sp", c_int, *lib.chase_hip_gev_backtransform.argtypes)
+_sig("chase_hip_gev_starttransform_sp", c_int, *lib.chase_hip_gev_backtransform.argtypes)
 
 
 def check(code, where):
@@ -411,6 +420,39 @@ class Context:
     def gev_starttransform(self, itype, n, ncols, U, ldu, X, ldx, cplx):
         """X <- U X (itype 1, 2) or U^{-H} X (itype 3): the inverse of gev_backtransform_itype"""
         check(lib.chase_hip_gev_starttransform(self.h, int(cplx), itype, n, ncols, U, ldu, X, ldx), "gev_starttransform")
+
+    # ---- the same on fp32 / complex fp32 data, itype 1 (capi_gev_sp.hip) ----
+    def gemm32op(self, opA, m, n, k, alpha, A, lda, B, ldb, beta, Cm, ldc, cplx):
+        """gemm32 with op(A) = N or C (real: T as well); N is gemm32 bit for bit, C is N on the explicit A^H bit for bit"""
+        op = opA.encode()[0:1]
+        if cplx:
+            check(lib.chase_hip_gemm_c_op(self.h, op, m, n, k, _c2(alpha), A, lda, B, ldb, _c2(beta), Cm, ldc), "gemm_c_op")
+        else:
+            check(lib.chase_hip_gemm_s_op(self.h, op, m, n, k, float(alpha), A, lda, B, ldb, float(beta), Cm, ldc), "gemm_s_op")
+
+    def trsm_left_upper_sp(self, op, n, nrhs, R, ldr, B, ldb, cplx):
+        check(lib.chase_hip_trsm_left_upper_sp(self.h, int(cplx), op.encode()[0:1], n, nrhs, R, ldr, B, ldb), "trsm_left_upper_sp")
+
+    def trmm_left_upper_sp(self, op, n, ncols, U, ldu, X, ldx, cplx):
+        check(lib.chase_hip_trmm_left_upper_sp(self.h, int(cplx), op.encode()[0:1], n, ncols, U, ldu, X, ldx), "trmm_left_upper_sp")
+
+    def potrf_upper_blocked_sp(self, n, A, lda, cplx, outer_nb=0):
+        info = lib.chase_hip_potrf_upper_blocked_sp(self.h, int(cplx), n, A, lda, outer_nb)
+        return info if info >= 0 else check(info, "potrf_upper_blocked_sp")
+
+    def hegst_upper_sp(self, n, A, lda, U, ldu, cplx):
+        check(lib.chase_hip_hegst_upper_sp(self.h, int(cplx), n, A, lda, U, ldu), "hegst_upper_sp")
+
+    def gev_reduce_sp(self, factor, n, A, lda, S, lds, cplx):
+        """factor 1: S <- U, then A <- U^{-H} A U^{-1} (returns the bad pivot if there is one, A untouched); factor 0: S holds U"""
+        info = lib.chase_hip_gev_reduce_sp(self.h, int(cplx), int(factor), n, A, lda, S, lds)
+        return info if info >= 0 else check(info, "gev_reduce_sp")
+
+    def gev_backtransform_sp(self, n, ncols, U, ldu, X, ldx, cplx):
+        check(lib.chase_hip_gev_backtransform_sp(self.h, int(cplx), n, ncols, U, ldu, X, ldx), "gev_backtransform_sp")
+
+    def gev_starttransform_sp(self, n, ncols, U, ldu, X, ldx, cplx):
+        check(lib.chase_hip_gev_starttransform_sp(self.h, int(cplx), n, ncols, U, ldu, X, ldx), "gev_starttransform_sp")
 
 
 # ---- non-GEMM kernels -------------------------------------------------------------------------------------------------
@@ -933,6 +975,101 @@ class SpSolver(Solver):
     def peek_v(self):
         out = np.empty((self.N, self.nev + self.nex), dtype=np.complex128 if self.cplx else np.float64, order="F")
         check(lib.chase_hip_solver_peek_v(self.h, self.ctx.h, out.ctypes.data, self.N), "peek_v")
+        return out
+
+
+class SpGevSolver:
+    """GevSolver at itype 1 on fp32 data: the lowest nev pairs of H x = lambda S x for H32, S32 float32 / complex64 (Fortran order,
+    S positive definite; the upper triangles are what is read).  Both are uploaded as they are and reduced in place on the device
+    by the fp32 drivers (S = U^H U, C = U^{-H} H U^{-1}); an SpSolver then works on C where it lies (self.solver).  While this
+    object lives the device holds C and U, 2 N^2 fp32 elements: no fp64 copy of H, S or C is ever made.  The surface is
+    GevSolver's; ritzv and residuals are fp64, the vectors fp32.  S not positive definite: ChaseHipError with .pivot."""
+
+    def __init__(self, ctx, H32, S32, nev, nex):
+        assert H32.ndim == 2 and H32.shape[0] == H32.shape[1] and S32.shape == H32.shape
+        assert H32.dtype in (np.float32, np.complex64) and S32.dtype in (np.float32, np.complex64), \
+            "SpGevSolver takes fp32 matrices: round them yourself"
+        self.ctx = ctx
+        self.cplx = bool(H32.dtype == np.complex64 or S32.dtype == np.complex64)
+        self.N, self.nev, self.nex = H32.shape[0], nev, nex
+        self.H, self.S = H32, S32                          # the originals, for gev_residuals()
+        self.dC, self.dU = self._dev(H32), self._dev(S32)
+        self.solver = None
+        info = ctx.gev_reduce_sp(1, self.N, self.dC.ptr, self.N, self.dU.ptr, self.N, self.cplx)
+        if info > 0:
+            self.close()
+            raise GevSolver._pivot_error(info)
+        self.solver = SpSolver(ctx, None, nev, nex, h_on_device_ptr=self.dC.ptr, N=self.N, cplx=self.cplx, ldh=self.N)
+
+    def _dt(self):
+        return np.complex64 if self.cplx else np.float32
+
+    def _dev(self, A):
+        return self.ctx.empty(A.shape, self._dt()).upload(A)
+
+    close = GevSolver.close
+    set = GevSolver.set
+    get = GevSolver.get
+    solve = GevSolver.solve
+    stats = GevSolver.stats
+    resid = GevSolver.resid
+    ritzv = GevSolver.ritzv
+    reduced = GevSolver.reduced
+    factor = GevSolver.factor
+    start_vectors = GevSolver.start_vectors
+
+    def update(self, H32, S32=None):
+        """GevSolver.update: the next pencil of a sequence, started from the previous vectors.  S32 = None: the overlap matrix
+        did not change, H is reduced with the stored factor (factor = 0, no Cholesky)."""
+        assert H32.shape == (self.N, self.N) and H32.dtype in (np.float32, np.complex64) and (H32.dtype == np.complex64) <= self.cplx
+        n, nc = self.N, self.nev + self.nex
+        if S32 is None:
+            self.dC.upload(H32)
+            self.ctx.gev_reduce_sp(0, n, self.dC.ptr, n, self.dU.ptr, n, self.cplx)
+        else:
+            assert S32.shape == H32.shape and S32.dtype in (np.float32, np.complex64) and (S32.dtype == np.complex64) <= self.cplx
+            dX = self._dev(self.solver.V)
+            try:
+                self.ctx.gev_backtransform_sp(n, nc, self.dU.ptr, n, dX.ptr, n, self.cplx)
+                self.dU.upload(S32)
+                self.dC.upload(H32)
+                info = self.ctx.gev_reduce_sp(1, n, self.dC.ptr, n, self.dU.ptr, n, self.cplx)
+                if info > 0:
+                    raise GevSolver._pivot_error(info)
+                self.ctx.gev_starttransform_sp(n, nc, self.dU.ptr, n, dX.ptr, n, self.cplx)
+                self.solver.V[...] = dX.download()
+            finally:
+                dX.free()
+            self.S = S32
+        self.H = H32
+        self.solver.set(approx=1)
+
+    def eigenpairs(self):
+        """(lambda[:nev] in fp64, X[:, :nev] in fp32): H X = S X diag(lambda), X^H S X = I"""
+        dX = self._dev(self.solver.V[:, :self.nev])
+        self.ctx.gev_backtransform_sp(self.N, self.nev, self.dU.ptr, self.N, dX.ptr, self.N, self.cplx)
+        X = dX.download()
+        dX.free()
+        return self.solver.ritzv[:self.nev].copy(), X
+
+    def gev_residuals(self):
+        """|| H x_j - lambda_j S x_j ||_2, j < nev, in fp64 from the ORIGINAL fp32 matrices (uploaded again for this: two more
+        N^2 fp32 blocks while it runs): products with fp32 operands and an fp64 result, norms in fp64"""
+        lam, X = self.eigenpairs()
+        n, k = self.N, self.nev
+        full = lambda A: np.triu(A) + np.triu(A, 1).conj().T          # the triangle the reduction read
+        dH, dS, dX = self._dev(full(self.H)), self._dev(full(self.S)), self._dev(X)
+        dt64 = np.complex128 if self.cplx else np.float64
+        dW, dV = self.ctx.empty((n, k), dt64), self.ctx.empty((n, k), dt64)
+        out = np.zeros(k)
+        try:
+            self.ctx.gemm32w("N", n, k, n, 1.0, dH.ptr, n, dX.ptr, n, 0.0, dW.ptr, n, self.cplx)
+            self.ctx.gemm32w("N", n, k, n, 1.0, dS.ptr, n, dX.ptr, n, 0.0, dV.ptr, n, self.cplx)
+            check(lib.chase_hip_resid_norms(self.ctx.h, int(self.cplx), n, k, dW.ptr, n, dV.ptr, n, lam.ctypes.data,
+                                            out.ctypes.data, 0), "resid_norms")
+        finally:
+            for d in (dH, dS, dX, dW, dV):
+                d.free()
         return out
 
 

@@ -287,6 +287,39 @@ int chase_hip_gemm_c(chase_hip_ctx* c, char opA, int m, int n, int k, const floa
     return gemm32(c, true, opA, m, n, k, alpha, (const float*)A, lda, (const float*)B, ldb, beta, (float*)C, ldc);
 }
 
+// C32 = alpha op(A32) B32 + beta C32, op(A) = N or C (real: T as well): chase_hip_gemm_s / _c with the k-contiguous operand path
+static int gemm32_op(chase_hip_ctx* c, bool cplx, char opA, int m, int n, int k, const float* alpha, const float* A, long lda,
+                     const float* B, long ldb, const float* beta, float* C, long ldc)
+{
+    (void)hipSetDevice(c->device);      // entry points may be called with another device current
+    const bool opn = opA == 'N' || opA == 'n';
+    const bool opc = opA == 'C' || opA == 'c' || (!cplx && (opA == 'T' || opA == 't'));
+    if (!opn && !opc)
+        return set_error(CHASE_HIP_EINVAL, cplx ? "gemm_c_op: opA must be 'N' or 'C'" : "gemm_s_op: opA must be 'N', 'C' or 'T'");
+    int rc = check_gemm(opA, m, n, k, A, lda, B, ldb, C, ldc);
+    if (rc || m == 0 || n == 0) return rc;
+    if (c->oplog_on) c->oplog_add(cplx ? (opn ? "gemm_c_opN" : "gemm_c_opC") : (opn ? "gemm_s_opN" : "gemm_s_opC"), m, n, k, c->phase * 100);
+    int e = gemm_f32_op(c->stream, cplx, opA, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, c->num_cu, c->phase == 1 ? 1 : 0);
+    if (e == GEMM_F32_EOP) return set_error(CHASE_HIP_EINVAL, "gemm_s_op / gemm_c_op: bad opA");
+    if (e) return hip_fail((hipError_t)e, "gemm_f32_op launch");
+    return 0;
+}
+
+int chase_hip_gemm_s_op(chase_hip_ctx* c, char opA, int m, int n, int k, float alpha, const float* A, long lda, const float* B,
+                        long ldb, float beta, float* C, long ldc)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "ctx == NULL");
+    return gemm32_op(c, false, opA, m, n, k, &alpha, A, lda, B, ldb, &beta, C, ldc);
+}
+
+int chase_hip_gemm_c_op(chase_hip_ctx* c, char opA, int m, int n, int k, const float alpha[2], const void* A, long lda,
+                        const void* B, long ldb, const float beta[2], void* C, long ldc)
+{
+    if (!c) return set_error(CHASE_HIP_EINVAL, "ctx == NULL");
+    if (!alpha || !beta) return set_error(CHASE_HIP_EINVAL, "gemm_c_op: NULL alpha/beta");
+    return gemm32_op(c, true, opA, m, n, k, alpha, (const float*)A, lda, (const float*)B, ldb, beta, (float*)C, ldc);
+}
+
 int chase_hip_gemm_s_bf16x3(chase_hip_ctx* c, char opA, int m, int n, int k, float alpha, const float* A, long lda, const float* B,
                             long ldb, float beta, float* C, long ldc)
 {

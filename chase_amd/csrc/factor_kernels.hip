@@ -11,6 +11,7 @@
 // LAPACK info semantics: the first non-positive (or NaN) pivot at global index p sets *info = p + 1 (first failure wins).
 
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "kernels.h"
 
 namespace chase_hip {
@@ -21,23 +22,39 @@ struct cd { double x, y; };
 __device__ __forceinline__ cd cmul_conj_a(cd a, cd b) { return cd{a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x}; } // conj(a)*b
 __device__ __forceinline__ cd cmul(cd a, cd b) { return cd{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 
-template <bool CPLX>
-__global__ __launch_bounds__(256) void potf2_trtri_kernel(double* __restrict__ A, long lda, int nb, int joff,
-                                                          double* __restrict__ Tinv, int* __restrict__ info)
+// Element i of a matrix stored as S = double (the fp64 entry points: the plain access) or S = float (the single-precision
+// generalized problem, capi_gev_sp.hip): widened on the way into LDS and rounded once on the way out, all arithmetic in fp64.
+template <bool CPLX, class S>
+__device__ __forceinline__ typename std::conditional<CPLX, cd, double>::type st_load(const S* p, long i)
+{
+    if constexpr (!CPLX) return (double)p[i];
+    else if constexpr (std::is_same<S, double>::value) return ((const cd*)p)[i];
+    else return cd{(double)p[2 * i], (double)p[2 * i + 1]};
+}
+template <bool CPLX, class S, class E>
+__device__ __forceinline__ void st_store(S* p, long i, E v)
+{
+    if constexpr (!CPLX) p[i] = (S)v;
+    else if constexpr (std::is_same<S, double>::value) ((cd*)p)[i] = v;
+    else { p[2 * i] = (S)v.x; p[2 * i + 1] = (S)v.y; }
+}
+
+template <bool CPLX, class S>
+__global__ __launch_bounds__(256) void potf2_trtri_kernel(S* __restrict__ A, long lda, int nb, int joff,
+                                                          S* __restrict__ Tinv, int* __restrict__ info)
 {
     using E = typename std::conditional<CPLX, cd, double>::type;
     __shared__ E s[FNB * FNB];          // column-major, ld = 64 (64 KiB complex / 32 KiB real)
     __shared__ double dinv[FNB];
     __shared__ int failed;
     const int tid = threadIdx.x;
-    E* Ag = (E*)A;
 
     if (tid == 0) failed = 0;
     for (int e = tid; e < FNB * FNB; e += 256) {
         const int i = e & 63, j = e >> 6;
         E v;
         if constexpr (CPLX) v = cd{0.0, 0.0}; else v = 0.0;
-        if (i < nb && j < nb && i <= j) v = Ag[(long)j * lda + i];
+        if (i < nb && j < nb && i <= j) v = st_load<CPLX>(A, (long)j * lda + i);
         s[e] = v;
     }
     __syncthreads();
@@ -83,7 +100,7 @@ __global__ __launch_bounds__(256) void potf2_trtri_kernel(double* __restrict__ A
     if (!bad) {
         for (int e = tid; e < FNB * FNB; e += 256) {
             const int i = e & 63, j = e >> 6;
-            if (i < nb && j < nb && i <= j) Ag[(long)j * lda + i] = s[e];
+            if (i < nb && j < nb && i <= j) st_store<CPLX>(A, (long)j * lda + i, s[e]);
         }
     }
 
@@ -104,7 +121,6 @@ __global__ __launch_bounds__(256) void potf2_trtri_kernel(double* __restrict__ A
         }
     }
     __syncthreads();
-    E* Tg = (E*)Tinv;
     for (int e = tid; e < FNB * FNB; e += 256) {
         const int i = e & 63, j = e >> 6;
         E v;
@@ -113,14 +129,14 @@ __global__ __launch_bounds__(256) void potf2_trtri_kernel(double* __restrict__ A
             if (i < j) v = s[j + i * FNB];
             else if (i == j) { if constexpr (CPLX) v = cd{dinv[i], 0.0}; else v = dinv[i]; }
         }
-        Tg[e] = v;
+        st_store<CPLX>(Tinv, e, v);
     }
 }
 
 // Batched inverse of the 64x64 upper-triangular diagonal blocks of R (n x n): Tinv[b] = R_bb^{-1}, one workgroup each.
-template <bool CPLX>
-__global__ __launch_bounds__(256) void trtri_diag_kernel(const double* __restrict__ R, long ldr, int n,
-                                                         double* __restrict__ Tinv)
+template <bool CPLX, class S>
+__global__ __launch_bounds__(256) void trtri_diag_kernel(const S* __restrict__ R, long ldr, int n,
+                                                         S* __restrict__ Tinv)
 {
     using E = typename std::conditional<CPLX, cd, double>::type;
     __shared__ E s[FNB * FNB];
@@ -128,12 +144,12 @@ __global__ __launch_bounds__(256) void trtri_diag_kernel(const double* __restric
     const int tid = threadIdx.x, b = blockIdx.x;
     const int j0 = b * FNB;
     const int nb = min(FNB, n - j0);
-    const E* Rg = (const E*)R + (long)j0 * ldr + j0;
+    const S* Rg = R + ((long)j0 * ldr + j0) * (CPLX ? 2 : 1);
     for (int e = tid; e < FNB * FNB; e += 256) {
         const int i = e & 63, j = e >> 6;
         E v;
         if constexpr (CPLX) v = cd{0.0, 0.0}; else v = 0.0;
-        if (i < nb && j < nb && i <= j) v = Rg[(long)j * ldr + i];
+        if (i < nb && j < nb && i <= j) v = st_load<CPLX>(Rg, (long)j * ldr + i);
         s[e] = v;
     }
     __syncthreads();
@@ -158,7 +174,7 @@ __global__ __launch_bounds__(256) void trtri_diag_kernel(const double* __restric
         }
     }
     __syncthreads();
-    E* Tg = (E*)Tinv + (long)b * FNB * FNB;
+    S* Tg = Tinv + (long)b * FNB * FNB * (CPLX ? 2 : 1);
     for (int e = tid; e < FNB * FNB; e += 256) {
         const int i = e & 63, j = e >> 6;
         E v;
@@ -167,24 +183,38 @@ __global__ __launch_bounds__(256) void trtri_diag_kernel(const double* __restric
             if (i < j) v = s[j + i * FNB];
             else if (i == j) { if constexpr (CPLX) v = cd{dinv[i], 0.0}; else v = dinv[i]; }
         }
-        Tg[e] = v;
+        st_store<CPLX>(Tg, e, v);
     }
 }
 
-int trtri_diag(hipStream_t st, bool cplx, const double* R, long ldr, int n, double* Tinv)
+template <class S>
+static int trtri_diag_t(hipStream_t st, bool cplx, const S* R, long ldr, int n, S* Tinv)
 {
     const int nblk = (n + FNB - 1) / FNB;
     if (nblk <= 0) return 0;
-    if (cplx) hipLaunchKernelGGL(trtri_diag_kernel<true>, dim3(nblk), dim3(256), 0, st, R, ldr, n, Tinv);
-    else      hipLaunchKernelGGL(trtri_diag_kernel<false>, dim3(nblk), dim3(256), 0, st, R, ldr, n, Tinv);
+    if (cplx) hipLaunchKernelGGL((trtri_diag_kernel<true, S>), dim3(nblk), dim3(256), 0, st, R, ldr, n, Tinv);
+    else      hipLaunchKernelGGL((trtri_diag_kernel<false, S>), dim3(nblk), dim3(256), 0, st, R, ldr, n, Tinv);
     return (int)hipGetLastError();
 }
 
+template <class S>
+static int potf2_trtri_t(hipStream_t st, bool cplx, S* A, long lda, int nb, int joff, S* Tinv, int* info_dev)
+{
+    if (cplx) hipLaunchKernelGGL((potf2_trtri_kernel<true, S>), dim3(1), dim3(256), 0, st, A, lda, nb, joff, Tinv, info_dev);
+    else      hipLaunchKernelGGL((potf2_trtri_kernel<false, S>), dim3(1), dim3(256), 0, st, A, lda, nb, joff, Tinv, info_dev);
+    return (int)hipGetLastError();
+}
+
+int trtri_diag(hipStream_t st, bool cplx, const double* R, long ldr, int n, double* Tinv) { return trtri_diag_t(st, cplx, R, ldr, n, Tinv); }
+int trtri_diag(hipStream_t st, bool cplx, const float* R, long ldr, int n, float* Tinv) { return trtri_diag_t(st, cplx, R, ldr, n, Tinv); }
+
 int potf2_trtri(hipStream_t st, bool cplx, double* A, long lda, int nb, int joff, double* Tinv, int* info_dev)
 {
-    if (cplx) hipLaunchKernelGGL(potf2_trtri_kernel<true>, dim3(1), dim3(256), 0, st, A, lda, nb, joff, Tinv, info_dev);
-    else      hipLaunchKernelGGL(potf2_trtri_kernel<false>, dim3(1), dim3(256), 0, st, A, lda, nb, joff, Tinv, info_dev);
-    return (int)hipGetLastError();
+    return potf2_trtri_t(st, cplx, A, lda, nb, joff, Tinv, info_dev);
+}
+int potf2_trtri(hipStream_t st, bool cplx, float* A, long lda, int nb, int joff, float* Tinv, int* info_dev)
+{
+    return potf2_trtri_t(st, cplx, A, lda, nb, joff, Tinv, info_dev);
 }
 
 } // namespace chase_hip

@@ -4,6 +4,7 @@
 //
 //   C = alpha * A * B + beta * C           column-major, op(A) = N, real fp32 or interleaved (re, im) complex fp32     (gemm_f32)
 //   C64 = alpha * op(A) * B + beta * C64   op(A) = N or C, A and B fp32, C / alpha / beta fp64                        (gemm_f32w)
+//   C = alpha * op(A) * B + beta * C       op(A) = C with the fp32 epilogue: instantiated in gemm_mfma_f32_op.hip     (gemm_f32_op)
 //
 // The second form is the product of the filter on a process grid (pChaseHip): every rank's partial product leaves the kernel in
 // fp64 and is summed over the ranks in fp64 by the collectives the fp64 path already has.  OPC reads A as a k x m array
@@ -241,6 +242,8 @@ int launch(hipStream_t st, const Args& a, int tag)
 
 } // namespace
 
+#ifndef CHASE_HIP_GEMM_F32_KERNEL_ONLY    // gemm_mfma_f32_op.hip takes the kernel above for instantiations of its own
+
 int gemm_f32w(hipStream_t st, bool cplx, char opA, int m, int n, int k, const double* alpha, const float* A, long lda,
               const float* B, long ldb, const double* beta, double* C, long ldc, int num_cu, int tag, double* ws, size_t ws_bytes,
               int min_rounds, int* pieces)
@@ -267,5 +270,7 @@ int gemm_f32(hipStream_t st, bool cplx, char opA, int m, int n, int k, const flo
         return bn == 64 ? launch<false, 1>(st, a, tag) : launch<false, 2>(st, a, tag);
     });
 }
+
+#endif // CHASE_HIP_GEMM_F32_KERNEL_ONLY
 
 } // namespace chase_hip

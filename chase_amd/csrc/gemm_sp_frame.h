@@ -240,6 +240,18 @@ int narrow(bool cplx, char opA, int m, int n, int k, const float* alpha, const f
     return launch(a);
 }
 
+// narrow with op(A) = N or C (real: T as well), A for op = C a k x m array: launch(a, opc) starts the kernel.  The generalized
+// problem's single-precision drivers (capi_gev_sp.hip); narrow itself keeps refusing anything but N.
+template <class Launch>
+int narrow_op(bool cplx, char opA, int m, int n, int k, const float* alpha, const float* A, long lda, const float* B, long ldb,
+              const float* beta, float* C, long ldc, int bn, Launch&& launch)
+{
+    const bool opn = opA == 'N' || opA == 'n';
+    const bool opc = opA == 'C' || opA == 'c' || (!cplx && (opA == 'T' || opA == 't'));
+    if (!opn && !opc) return GEMM_F32_EOP;
+    return narrow(cplx, 'N', m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, bn, [&](const Args& a) { return launch(a, opc); });
+}
+
 // C64 = alpha op(A) B + beta C64 with fp64 scalars, op(A) = N or C (real: T as well): launch(a, opc) starts the kernel on
 // a.total x a.sk workgroups.  sp.sk > 1 (split_plan): the pieces go to the slabs in ws (at least sp.slab_bytes) with
 // alpha = 1, beta = 0, and sp_slab_reduce forms C from them on the same stream.

@@ -35,6 +35,10 @@ int gemm_f64_plan(bool cplx, char opA, int m, int n, int k, long lda, long ldb, 
 constexpr int GEMM_F32_EOP = -77002;
 int gemm_f32(hipStream_t st, bool cplx, char opA, int m, int n, int k, const float* alpha, const float* A, long lda, const float* B,
              long ldb, const float* beta, float* C, long ldc, int num_cu, int tag = 0);
+// gemm_f32 with op(A) = N or C (real: T as well), A for op = C a k x m array: op N is gemm_f32 bit for bit, op C is op N on the
+// explicitly formed A^H bit for bit.  The product of the single-precision generalized problem (capi_gev_sp.hip).
+int gemm_f32_op(hipStream_t st, bool cplx, char opA, int m, int n, int k, const float* alpha, const float* A, long lda,
+                const float* B, long ldb, const float* beta, float* C, long ldc, int num_cu, int tag = 0);
 // the same product written and scaled in fp64: C64 = alpha op(A32) B32 + beta C64, op(A) = N or C (real: T as well), A for
 // op = C a k x m array.  alpha / beta point to 1 or 2 host doubles.  The product of the filter on a grid: the partial products
 // of the ranks are summed in fp64.  Whole K unless gemm_min_rounds asks for pieces; bitwise reproducible either way:
@@ -147,5 +151,19 @@ int add_upper(hipStream_t st, const double* src, long ld_src, double* dst, long 
 int trmm_diag(hipStream_t st, bool cplx, bool op_c, const double* U, long ldu, double* X, long ldx, int nb, int ncols);
 // A (n x n) <- A^H in place
 int conj_transpose_inplace(hipStream_t st, bool cplx, double* A, long lda, int n);
+
+// ---- the same cores on fp32 storage (capi_gev_sp.hip) ----
+// potf2_trtri / trtri_diag / hegs2_diag: the kernels above instantiated for float matrices - loads widened, all arithmetic in
+// fp64 registers and LDS, one rounding on the way out (Tinv is fp32 too: it feeds the fp32 product).  The helpers address floats.
+int potf2_trtri(hipStream_t st, bool cplx, float* A, long lda, int nb, int joff, float* Tinv, int* info_dev);
+int trtri_diag(hipStream_t st, bool cplx, const float* R, long ldr, int n, float* Tinv);
+int hegs2_diag(hipStream_t st, bool cplx, float* A, long lda, const float* U, long ldu, int nb);
+int add_upper(hipStream_t st, const float* src, long ld_src, float* dst, long ld_dst, int n, int ept);
+int conj_transpose_inplace(hipStream_t st, bool cplx, float* A, long lda, int n);
+int mirror_upper(hipStream_t st, float* A, long lda, int n, int ept);
+int mirror_lower(hipStream_t st, float* A, long lda, int n, int ept, int zero_diag_imag = 1);
+int copy2d_sp(hipStream_t st, const float* src, long ld_src_f, float* dst, long ld_dst_f, long mf, int ncols);   // sp_kernels.hip
+// trmm_diag on fp32 data: v_mfma_f32_16x16x4_f32, fp32 accumulation
+int trmm_diag_sp(hipStream_t st, bool cplx, bool op_c, const float* U, long ldu, float* X, long ldx, int nb, int ncols);
 
 } // namespace chase_hip

@@ -186,6 +186,14 @@ inline int ept_of(int cplx) { return cplx ? 2 : 1; }
 
 namespace chase_hip {
 
+int copy2d_sp(hipStream_t st, const float* src, long ld_src_f, float* dst, long ld_dst_f, long mf, int ncols)
+{
+    if (mf <= 0 || ncols <= 0) return 0;
+    const int vec = (ld_src_f & 3) == 0 && (ld_dst_f & 3) == 0 && a16(src) && a16(dst);
+    hipLaunchKernelGGL(copy2d_sp_kernel, grid2(mf, ncols), dim3(256), 0, st, src, ld_src_f, dst, ld_dst_f, mf, ncols, vec);
+    return (int)hipGetLastError();
+}
+
 int scale_rows_sp(hipStream_t st, float* X, long ldx_f, long row0_f, long mf, int ncols, float s)
 {
     if (row0_f >= mf || ncols <= 0) return 0;

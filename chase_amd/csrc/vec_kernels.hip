@@ -470,12 +470,13 @@ __global__ void pack_upper_kernel(const double* __restrict__ A, long lda, int n,
 }
 
 // A[i,j] = conj(A[j,i]) for i > j: rebuild the strictly-lower triangle from the upper one
-__global__ void mirror_upper_kernel(double* __restrict__ A, long lda, int n, int ept)
+template <class T>
+__global__ void mirror_upper_kernel(T* __restrict__ A, long lda, int n, int ept)
 {
     const int j = blockIdx.x;
     for (int i = j + 1 + threadIdx.x; i < n; i += blockDim.x) {
-        const double* s = A + ((long)i * lda + j) * ept;        // A[j,i] (upper)
-        double* d = A + ((long)j * lda + i) * ept;              // A[i,j] (lower)
+        const T* s = A + ((long)i * lda + j) * ept;             // A[j,i] (upper)
+        T* d = A + ((long)j * lda + i) * ept;                   // A[i,j] (lower)
         d[0] = s[0];
         if (ept == 2) d[1] = -s[1];
     }
@@ -568,13 +569,14 @@ __global__ __launch_bounds__(256) void hash64_kernel(const unsigned long long* _
 }
 
 // A[i,j] = conj(A[j,i]) for i < j (rebuild the strictly-upper triangle from the lower one) and Im A[j,j] = 0
-__global__ void mirror_lower_kernel(double* __restrict__ A, long lda, int n, int ept, int zero_diag_imag)
+template <class T>
+__global__ void mirror_lower_kernel(T* __restrict__ A, long lda, int n, int ept, int zero_diag_imag)
 {
     const int j = blockIdx.x;                                   // column of the lower triangle being read
-    if (threadIdx.x == 0 && ept == 2 && zero_diag_imag) A[((long)j * lda + j) * 2 + 1] = 0.0;
+    if (threadIdx.x == 0 && ept == 2 && zero_diag_imag) A[((long)j * lda + j) * 2 + 1] = T(0);
     for (int i = j + 1 + threadIdx.x; i < n; i += blockDim.x) {
-        const double* s = A + ((long)j * lda + i) * ept;        // A[i,j] (lower)
-        double* d = A + ((long)i * lda + j) * ept;              // A[j,i] (upper)
+        const T* s = A + ((long)j * lda + i) * ept;             // A[i,j] (lower)
+        T* d = A + ((long)i * lda + j) * ept;                   // A[j,i] (upper)
         d[0] = s[0];
         if (ept == 2) d[1] = -s[1];
     }
@@ -795,13 +797,25 @@ int unpack_upper(hipStream_t st, double* P, int n, int ept, double* A, long lda)
 int mirror_lower(hipStream_t st, double* A, long lda, int n, int ept, int zero_diag_imag)
 {
     if (n <= 0) return 0;
-    hipLaunchKernelGGL(mirror_lower_kernel, dim3(n), dim3(128), 0, st, A, lda, n, ept, zero_diag_imag);
+    hipLaunchKernelGGL(mirror_lower_kernel<double>, dim3(n), dim3(128), 0, st, A, lda, n, ept, zero_diag_imag);
     return (int)hipGetLastError();
 }
 int mirror_upper(hipStream_t st, double* A, long lda, int n, int ept)
 {
     if (n <= 1) return 0;
-    hipLaunchKernelGGL(mirror_upper_kernel, dim3(n), dim3(128), 0, st, A, lda, n, ept);
+    hipLaunchKernelGGL(mirror_upper_kernel<double>, dim3(n), dim3(128), 0, st, A, lda, n, ept);
+    return (int)hipGetLastError();
+}
+int mirror_lower(hipStream_t st, float* A, long lda, int n, int ept, int zero_diag_imag)
+{
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(mirror_lower_kernel<float>, dim3(n), dim3(128), 0, st, A, lda, n, ept, zero_diag_imag);
+    return (int)hipGetLastError();
+}
+int mirror_upper(hipStream_t st, float* A, long lda, int n, int ept)
+{
+    if (n <= 1) return 0;
+    hipLaunchKernelGGL(mirror_upper_kernel<float>, dim3(n), dim3(128), 0, st, A, lda, n, ept);
     return (int)hipGetLastError();
 }
 

@@ -74,6 +74,57 @@ void backtransform(int cplx, int itype, bool start, int N, int ncols, void* U, i
     *info = rc;
 }
 
+// ---- single precision (capi_gev_sp.hip): float / float _Complex host matrices, itype 1 only ----
+struct DevMatSp {                                 // DevMat with 4-byte scalars
+    chase_hip_ctx* c;
+    void* p = nullptr;
+    explicit DevMatSp(chase_hip_ctx* c_) : c(c_) {}
+    ~DevMatSp() { if (p) chase_hip_free(c, p); }
+    int up(int cplx, int m, int n, const void* host, int ldh)
+    {
+        int rc = chase_hip_malloc(c, &p, (size_t)m * n * (cplx ? 8 : 4));
+        return rc ? rc : chase_hip_upload_matrix_sp(c, cplx, m, n, host, ldh, p, m);
+    }
+    int down(int cplx, int m, int n, void* host, int ldh) { return chase_hip_download_matrix_sp(c, cplx, m, n, p, m, host, ldh); }
+};
+
+void reduce_sp(int cplx, int itype, int factor, int N, void* H, int ldh, void* S, int lds, int* info)
+{
+    if (!info) return;
+    *info = CHASE_HIP_EINVAL;
+    if (itype != 1 || (factor != 0 && factor != 1)) return;       // itype 2 / 3: fp64 only
+    if (N < 0 || ldh < N || lds < N || (N > 0 && (!H || !S))) return;
+    *info = 0;
+    if (N == 0) return;
+    if (!ensure_ctx()) { *info = CHASE_HIP_ENODEV; return; }
+    DevMatSp dH(g_gev_ctx), dS(g_gev_ctx);
+    int rc = dH.up(cplx, N, N, H, ldh);
+    if (!rc) rc = dS.up(cplx, N, N, S, lds);
+    if (!rc) rc = chase_hip_gev_reduce_sp(g_gev_ctx, cplx, factor, N, dH.p, N, dS.p, N);
+    if (rc) { *info = rc; return; }               // S not positive definite (rc > 0) or a runtime error: H and S as they were
+    rc = dH.down(cplx, N, N, H, ldh);
+    if (!rc && factor) rc = dS.down(cplx, N, N, S, lds);
+    *info = rc;
+}
+
+void backtransform_sp(int cplx, int itype, bool start, int N, int ncols, void* U, int ldu, void* V, int ldv, int* info)
+{
+    if (!info) return;
+    *info = CHASE_HIP_EINVAL;
+    if (itype != 1) return;
+    if (N < 0 || ncols < 0 || ldu < N || ldv < N || (N > 0 && (!U || (ncols > 0 && !V)))) return;
+    *info = 0;
+    if (N == 0 || ncols == 0) return;
+    if (!ensure_ctx()) { *info = CHASE_HIP_ENODEV; return; }
+    DevMatSp dU(g_gev_ctx), dV(g_gev_ctx);
+    int rc = dU.up(cplx, N, N, U, ldu);
+    if (!rc) rc = dV.up(cplx, N, ncols, V, ldv);
+    if (!rc) rc = start ? chase_hip_gev_starttransform_sp(g_gev_ctx, cplx, N, ncols, dU.p, N, dV.p, N)
+                        : chase_hip_gev_backtransform_sp(g_gev_ctx, cplx, N, ncols, dU.p, N, dV.p, N);
+    if (!rc) rc = dV.down(cplx, N, ncols, V, ldv);
+    *info = rc;
+}
+
 // the _itype entry points take itype 1 .. 3 only
 bool itype_ok(int itype, int* info)
 {
@@ -117,5 +168,41 @@ void dchase_gev_starttransform_(int* itype, int* N, int* ncols, double* U, int* 
 void zchase_gev_starttransform_(int* itype, int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info)
 {
     if (itype_ok(*itype, info)) backtransform(1, *itype, true, *N, *ncols, U, *ldu, V, *ldv, info);
+}
+
+// single precision: the d / z signatures with float data; itype 2 / 3: *info = CHASE_HIP_EINVAL
+void schase_gev_reduce_(int* N, float* H, int* ldh, float* S, int* lds, int* info) { reduce_sp(0, 1, 1, *N, H, *ldh, S, *lds, info); }
+void cchase_gev_reduce_(int* N, void* H, int* ldh, void* S, int* lds, int* info) { reduce_sp(1, 1, 1, *N, H, *ldh, S, *lds, info); }
+void schase_gev_backtransform_(int* N, int* ncols, float* U, int* ldu, float* V, int* ldv, int* info)
+{
+    backtransform_sp(0, 1, false, *N, *ncols, U, *ldu, V, *ldv, info);
+}
+void cchase_gev_backtransform_(int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info)
+{
+    backtransform_sp(1, 1, false, *N, *ncols, U, *ldu, V, *ldv, info);
+}
+void schase_gev_reduce_itype_(int* itype, int* factor, int* N, float* H, int* ldh, float* S, int* lds, int* info)
+{
+    reduce_sp(0, *itype, *factor, *N, H, *ldh, S, *lds, info);
+}
+void cchase_gev_reduce_itype_(int* itype, int* factor, int* N, void* H, int* ldh, void* S, int* lds, int* info)
+{
+    reduce_sp(1, *itype, *factor, *N, H, *ldh, S, *lds, info);
+}
+void schase_gev_backtransform_itype_(int* itype, int* N, int* ncols, float* U, int* ldu, float* V, int* ldv, int* info)
+{
+    backtransform_sp(0, *itype, false, *N, *ncols, U, *ldu, V, *ldv, info);
+}
+void cchase_gev_backtransform_itype_(int* itype, int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info)
+{
+    backtransform_sp(1, *itype, false, *N, *ncols, U, *ldu, V, *ldv, info);
+}
+void schase_gev_starttransform_(int* itype, int* N, int* ncols, float* U, int* ldu, float* V, int* ldv, int* info)
+{
+    backtransform_sp(0, *itype, true, *N, *ncols, U, *ldu, V, *ldv, info);
+}
+void cchase_gev_starttransform_(int* itype, int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info)
+{
+    backtransform_sp(1, *itype, true, *N, *ncols, U, *ldu, V, *ldv, info);
 }
 }

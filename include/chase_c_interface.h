@@ -76,7 +76,10 @@ void cchase_get_eigenpairs_(void* LEigsV, int* ld, float* ritzv);
  * reduced problem.  A warm step of a sequence: reduce_itype on the new pencil -> starttransform of the previous step's
  * back-transformed block, all nev + nex columns, into V -> ?chase_ with mode 'A' and the previous ritzv -> backtransform_itype
  * (examples/c_gev_sequence.c).  itype outside 1 .. 3 or factor outside 0 / 1: *info = CHASE_HIP_EINVAL.
- * Not provided: grid solvers, single precision, pseudo-Hermitian pencils. */
+ * schase_gev_* / cchase_gev_*: the same entry points on float / float _Complex matrices, served by the single-precision drivers
+ * (chase_hip_gev_reduce_sp and friends: nothing is widened to fp64) and used around schase_init_ / schase_ / schase_finalize_
+ * (examples/c_gev_sp.c).  They cover itype 1 only: itype 2 or 3 gives *info = CHASE_HIP_EINVAL.
+ * Not provided: grid solvers, pseudo-Hermitian pencils. */
 void dchase_gev_reduce_(int* N, double* H, int* ldh, double* S, int* lds, int* info);
 void zchase_gev_reduce_(int* N, void* H, int* ldh, void* S, int* lds, int* info);
 void dchase_gev_backtransform_(int* N, int* ncols, double* U, int* ldu, double* V, int* ldv, int* info);
@@ -87,6 +90,16 @@ void dchase_gev_backtransform_itype_(int* itype, int* N, int* ncols, double* U, 
 void zchase_gev_backtransform_itype_(int* itype, int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info);
 void dchase_gev_starttransform_(int* itype, int* N, int* ncols, double* U, int* ldu, double* V, int* ldv, int* info);
 void zchase_gev_starttransform_(int* itype, int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info);
+void schase_gev_reduce_(int* N, float* H, int* ldh, float* S, int* lds, int* info);
+void cchase_gev_reduce_(int* N, void* H, int* ldh, void* S, int* lds, int* info);
+void schase_gev_backtransform_(int* N, int* ncols, float* U, int* ldu, float* V, int* ldv, int* info);
+void cchase_gev_backtransform_(int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info);
+void schase_gev_reduce_itype_(int* itype, int* factor, int* N, float* H, int* ldh, float* S, int* lds, int* info);
+void cchase_gev_reduce_itype_(int* itype, int* factor, int* N, void* H, int* ldh, void* S, int* lds, int* info);
+void schase_gev_backtransform_itype_(int* itype, int* N, int* ncols, float* U, int* ldu, float* V, int* ldv, int* info);
+void cchase_gev_backtransform_itype_(int* itype, int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info);
+void schase_gev_starttransform_(int* itype, int* N, int* ncols, float* U, int* ldu, float* V, int* ldv, int* info);
+void cchase_gev_starttransform_(int* itype, int* N, int* ncols, void* U, int* ldu, void* V, int* ldv, int* info);
 void chase_enable_sym_check_(int* flag);    /* interface/chase_c_interface.cpp:4055: flag kept for callers that set it */
 /* unified configuration setters and build queries (interface/chase_c_interface.h:207-238): act on the live solver instance
  * (sequential or distributed), silent when none is initialised */

@@ -89,6 +89,14 @@ int chase_hip_gemm_s(chase_hip_ctx* ctx, char opA, int m, int n, int k, float al
                      long ldb, float beta, float* C, long ldc);
 int chase_hip_gemm_c(chase_hip_ctx* ctx, char opA, int m, int n, int k, const float alpha[2], const void* A, long lda,
                      const void* B, long ldb, const float beta[2], void* C, long ldc);
+/* gemm_s / gemm_c with op(A): C32 = alpha op(A32) B32 + beta C32, opA 'N' or 'C' (real: 'T' as well; anything else:
+ * CHASE_HIP_EINVAL); A is m x k for 'N' (lda >= m) and k x m for 'C' (lda >= k).  'N' is gemm_s / gemm_c bit for bit; 'C' is 'N' on
+ * the explicitly formed A^H bit for bit (the same LDS image and MFMA order).  The product of the single-precision generalized
+ * problem below; gemm_s / gemm_c themselves keep refusing anything but 'N'. */
+int chase_hip_gemm_s_op(chase_hip_ctx* ctx, char opA, int m, int n, int k, float alpha, const float* A, long lda, const float* B,
+                        long ldb, float beta, float* C, long ldc);
+int chase_hip_gemm_c_op(chase_hip_ctx* ctx, char opA, int m, int n, int k, const float alpha[2], const void* A, long lda,
+                        const void* B, long ldb, const float beta[2], void* C, long ldc);
 /* The fp32-input product with an fp64 result: C64 = alpha op(A32) B32 + beta C64, A and B real fp32 / interleaved complex fp32,
  * C, alpha and beta fp64.  opA is 'N' or 'C' (real: 'T' as well; anything else: CHASE_HIP_EINVAL); A is m x k for 'N' (lda >= m)
  * and k x m for 'C' (lda >= k).  The accumulation runs on the f32-input matrix cores exactly as in gemm_s / _c; alpha acc + beta C
@@ -429,6 +437,19 @@ int chase_hip_gev_backtransform_itype(chase_hip_ctx* ctx, int cplx, int itype, i
  * pencil - the previous step's of a sequence - become the start block of the reduced problem (mode 'A' / approx) */
 int chase_hip_gev_starttransform(chase_hip_ctx* ctx, int cplx, int itype, int n, int ncols, const void* U, long ldu, void* X,
                                  long ldx);
+/* ---- The generalized problem in single precision: H x = lambda S x (itype 1 only) on real fp32 / interleaved complex fp32 data.
+ * The entry points above with float matrices, the same contracts (upper storage, the strictly lower triangle of S / U / R
+ * neither read nor written, rows beyond n untouched, info > 0 the first non-positive pivot) and the same block sizes; nothing
+ * of size n^2 is widened to fp64.  Products run on the fp32 matrix cores (chase_hip_gemm_s_op / _c_op), the 64-wide diagonal
+ * cores compute in fp64 and round once.  hegst_upper_sp has the two-full-solve form only; reduce / backtransform /
+ * starttransform are the itype 1 forms: gev_reduce_sp(factor = 0) reuses the U stored in S. */
+int chase_hip_trsm_left_upper_sp(chase_hip_ctx* ctx, int cplx, char op, int n, int nrhs, const void* R, long ldr, void* B, long ldb);
+int chase_hip_trmm_left_upper_sp(chase_hip_ctx* ctx, int cplx, char op, int n, int ncols, const void* U, long ldu, void* X, long ldx);
+int chase_hip_potrf_upper_blocked_sp(chase_hip_ctx* ctx, int cplx, int n, void* A, long lda, int outer_nb);
+int chase_hip_hegst_upper_sp(chase_hip_ctx* ctx, int cplx, int n, void* A, long lda, const void* U, long ldu);
+int chase_hip_gev_reduce_sp(chase_hip_ctx* ctx, int cplx, int factor, int n, void* A, long lda, void* S, long lds);
+int chase_hip_gev_backtransform_sp(chase_hip_ctx* ctx, int cplx, int n, int ncols, const void* U, long ldu, void* X, long ldx);
+int chase_hip_gev_starttransform_sp(chase_hip_ctx* ctx, int cplx, int n, int ncols, const void* U, long ldu, void* X, long ldx);
 /* variant 1 = cholQR1, 2 = cholQR2, 3 = shiftedcholQR2 (linalg/internal/cpu/cholqr1.hpp:41-189); returns info */
 int chase_hip_cholqr(chase_hip_ctx* ctx, int cplx, int m, int n, void* V, long ldv, void* A, long lda, int variant,
                      long m_global);
