@@ -29,6 +29,7 @@ _sig("chase_hip_grid_group_active", c_int, c_void_p, c_int)
 _sig("chase_hip_grid_info", c_int, c_void_p, P(c_int), P(c_int), P(c_int), P(c_int))
 _sig("chase_hip_grid_allreduce", c_int, c_void_p, c_int, c_void_p, c_size_t, c_int)
 _sig("chase_hip_grid_bcast", c_int, c_void_p, c_int, c_void_p, c_size_t, c_int, c_int)
+_sig("chase_hip_houseqr_dist", c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_long, c_long)
 _sig("chase_hip_grid_wait", c_int, c_void_p)
 _sig("chase_hip_grid_agree_max", c_int, c_void_p, P(c_int))
 SR_FN = C.CFUNCTYPE(c_int, c_void_p, c_int, P(c_double), c_size_t, c_int, P(c_double), c_size_t, c_int)
