@@ -421,7 +421,7 @@ class Context:
         """X <- U X (itype 1, 2) or U^{-H} X (itype 3): the inverse of gev_backtransform_itype"""
         check(lib.chase_hip_gev_starttransform(self.h, int(cplx), itype, n, ncols, U, ldu, X, ldx), "gev_starttransform")
 
-    # ---- the same on fp32 / complex fp32 data, itype 1 (capi_gev_sp.hip) ----
+    # ---- the same on fp32 / complex fp32 data, itype 1 (the _sp entry points of capi_gev.hip) ----
     def gemm32op(self, opA, m, n, k, alpha, A, lda, B, ldb, beta, Cm, ldc, cplx):
         """gemm32 with op(A) = N or C (real: T as well); N is gemm32 bit for bit, C is N on the explicit A^H bit for bit"""
         op = opA.encode()[0:1]
@@ -818,16 +818,13 @@ class GevSolver:
         self.cplx = bool(np.iscomplexobj(H) or np.iscomplexobj(S))
         self.N, self.nev, self.nex = H.shape[0], nev, nex
         self.H, self.S = H, S                              # the originals, for gev_residuals()
-        self.dC, self.dU = ctx.array(H.astype(self._dt(), copy=False)), ctx.array(S.astype(self._dt(), copy=False))
+        self.dC, self.dU = self._dev(H), self._dev(S)
         self.solver = None
-        if itype == 1:
-            info = ctx.gev_reduce(self.N, self.dC.ptr, self.N, self.dU.ptr, self.N, self.cplx)
-        else:
-            info = ctx.gev_reduce_itype(itype, 1, self.N, self.dC.ptr, self.N, self.dU.ptr, self.N, self.cplx)
+        info = self._reduce(1, first=True)
         if info > 0:
             self.close()
             raise self._pivot_error(info)
-        self.solver = Solver(ctx, None, nev, nex, h_on_device_ptr=self.dC.ptr, N=self.N, cplx=self.cplx)
+        self.solver = self._solver_class(ctx, None, nev, nex, h_on_device_ptr=self.dC.ptr, N=self.N, cplx=self.cplx)
 
     @staticmethod
     def _pivot_error(info):
@@ -835,8 +832,44 @@ class GevSolver:
         err.pivot = info
         return err
 
+    # ---- what depends on the precision (SpGevSolver overrides these) ----
+    _solver_class = Solver
+
     def _dt(self):
         return np.complex128 if self.cplx else np.float64
+
+    def _accepts(self, A):
+        """whether a host matrix may be given as H or S: anything that converts to the fp64 type exactly"""
+        return bool(np.iscomplexobj(A)) <= self.cplx
+
+    def _dev(self, A):
+        """a device copy of a host array in this solver's type"""
+        return self.ctx.empty(A.shape, self._dt()).upload(A)
+
+    def _reduce(self, factor, first=False):
+        """dC <- its reduction with dU (factor 1: dU <- U first); the constructor's call at itype 1 is the plain entry point"""
+        a = (self.N, self.dC.ptr, self.N, self.dU.ptr, self.N, self.cplx)
+        return self.ctx.gev_reduce(*a) if first and self.itype == 1 else self.ctx.gev_reduce_itype(self.itype, factor, *a)
+
+    def _backtransform(self, dX, ncols, plain=False):
+        """plain: the itype-free entry point (eigenpairs() at itype 1)"""
+        a = (self.N, ncols, self.dU.ptr, self.N, dX.ptr, self.N, self.cplx)
+        if plain and self.itype == 1:
+            self.ctx.gev_backtransform(*a)
+        else:
+            self.ctx.gev_backtransform_itype(self.itype, *a)
+
+    def _starttransform(self, dX, ncols):
+        self.ctx.gev_starttransform(self.itype, self.N, ncols, self.dU.ptr, self.N, dX.ptr, self.N, self.cplx)
+
+    def _residual_products(self, products):
+        """dW <- dA dB for every (dA, dB, dW), dA N x N: fresh four-multiplication fp64 products (phase 3)"""
+        try:
+            check(lib.chase_hip_ctx_set_phase(self.ctx.h, 3), "set_phase")
+            for dA, dB, dW in products:
+                self.ctx.gemm("N", self.N, dB.shape[1], self.N, 1.0, dA.ptr, self.N, dB.ptr, self.N, 0.0, dW.ptr, self.N, self.cplx)
+        finally:
+            lib.chase_hip_ctx_set_phase(self.ctx.h, 0)
 
     def close(self):
         if self.solver:
@@ -875,22 +908,22 @@ class GevSolver:
         S given: all nev + nex columns of the block are back-transformed with the old factor, S and H are uploaded and reduced,
         and the block is start-transformed with the new factor - all on the device.  S = None: the overlap matrix did not change;
         only H is uploaded and reduced with the stored factor (no Cholesky), and the block stays as it is."""
-        assert H.shape == (self.N, self.N) and bool(np.iscomplexobj(H)) <= self.cplx
-        n, nc, dt = self.N, self.nev + self.nex, self._dt()
+        assert H.shape == (self.N, self.N) and self._accepts(H)
+        nc = self.nev + self.nex
         if S is None:
-            self.dC.upload(np.asfortranarray(H.astype(dt, copy=False)))
-            self.ctx.gev_reduce_itype(self.itype, 0, n, self.dC.ptr, n, self.dU.ptr, n, self.cplx)
+            self.dC.upload(H)
+            self._reduce(0)
         else:
-            assert S.shape == H.shape and bool(np.iscomplexobj(S)) <= self.cplx
-            dX = self.ctx.array(self.solver.V)
+            assert S.shape == H.shape and self._accepts(S)
+            dX = self._dev(self.solver.V)
             try:
-                self.ctx.gev_backtransform_itype(self.itype, n, nc, self.dU.ptr, n, dX.ptr, n, self.cplx)
-                self.dU.upload(np.asfortranarray(S.astype(dt, copy=False)))
-                self.dC.upload(np.asfortranarray(H.astype(dt, copy=False)))
-                info = self.ctx.gev_reduce_itype(self.itype, 1, n, self.dC.ptr, n, self.dU.ptr, n, self.cplx)
+                self._backtransform(dX, nc)
+                self.dU.upload(S)
+                self.dC.upload(H)
+                info = self._reduce(1)
                 if info > 0:
                     raise self._pivot_error(info)
-                self.ctx.gev_starttransform(self.itype, n, nc, self.dU.ptr, n, dX.ptr, n, self.cplx)
+                self._starttransform(dX, nc)
                 self.solver.V[...] = dX.download()
             finally:
                 dX.free()
@@ -900,41 +933,35 @@ class GevSolver:
 
     def eigenpairs(self):
         """(lambda[:nev], X[:, :nev]): itype 1, H X = S X diag(lambda) and X^H S X = I; itype 2, H S X = X diag(lambda) and
-        X^H S X = I; itype 3, S H X = X diag(lambda) and X^H S^{-1} X = I"""
-        dX = self.ctx.array(self.solver.V[:, :self.nev])
-        if self.itype == 1:
-            self.ctx.gev_backtransform(self.N, self.nev, self.dU.ptr, self.N, dX.ptr, self.N, self.cplx)
-        else:
-            self.ctx.gev_backtransform_itype(self.itype, self.N, self.nev, self.dU.ptr, self.N, dX.ptr, self.N, self.cplx)
+        X^H S X = I; itype 3, S H X = X diag(lambda) and X^H S^{-1} X = I.  lambda is fp64, X of the solver's type."""
+        dX = self._dev(self.solver.V[:, :self.nev])
+        self._backtransform(dX, self.nev, plain=True)
         X = dX.download()
         dX.free()
         return self.solver.ritzv[:self.nev].copy(), X
 
     def gev_residuals(self):
         """|| H x_j - lambda_j S x_j ||_2 (itype 1), || H S x_j - lambda_j x_j ||_2 (itype 2) or || S H x_j - lambda_j x_j ||_2
-        (itype 3), j < nev, from fresh four-multiplication products (phase 3) with the ORIGINAL H and S, which are uploaded
-        again for this (two more N^2 blocks while it runs)"""
+        (itype 3), j < nev, in fp64 from fresh products (_residual_products) with the ORIGINAL H and S, which are uploaded again
+        for this (two more N^2 blocks while it runs)"""
         lam, X = self.eigenpairs()
-        n, k, dt = self.N, self.nev, self._dt()
+        n, k = self.N, self.nev
         full = lambda A: np.triu(A) + np.triu(A, 1).conj().T          # the triangle the reduction read
-        dH, dS, dX = self.ctx.array(full(self.H).astype(dt)), self.ctx.array(full(self.S).astype(dt)), self.ctx.array(X)
-        dW, dV = self.ctx.empty((n, k), dt), self.ctx.empty((n, k), dt)
+        dH, dS, dX = self._dev(full(self.H)), self._dev(full(self.S)), self._dev(X)
+        dt64 = np.complex128 if self.cplx else np.float64
+        dW, dV = self.ctx.empty((n, k), dt64), self.ctx.empty((n, k), dt64)
         out = np.zeros(k)
         try:
-            check(lib.chase_hip_ctx_set_phase(self.ctx.h, 3), "set_phase")
             if self.itype == 1:
-                self.ctx.gemm("N", n, k, n, 1.0, dH.ptr, n, dX.ptr, n, 0.0, dW.ptr, n, self.cplx)
-                self.ctx.gemm("N", n, k, n, 1.0, dS.ptr, n, dX.ptr, n, 0.0, dV.ptr, n, self.cplx)
+                self._residual_products([(dH, dX, dW), (dS, dX, dV)])
                 rhs = dV
             else:
                 first, second = (dS, dH) if self.itype == 2 else (dH, dS)
-                self.ctx.gemm("N", n, k, n, 1.0, first.ptr, n, dX.ptr, n, 0.0, dV.ptr, n, self.cplx)
-                self.ctx.gemm("N", n, k, n, 1.0, second.ptr, n, dV.ptr, n, 0.0, dW.ptr, n, self.cplx)
+                self._residual_products([(first, dX, dV), (second, dV, dW)])
                 rhs = dX
             check(lib.chase_hip_resid_norms(self.ctx.h, int(self.cplx), n, k, dW.ptr, n, rhs.ptr, n, lam.ctypes.data,
                                             out.ctypes.data, 0), "resid_norms")
         finally:
-            lib.chase_hip_ctx_set_phase(self.ctx.h, 0)
             for d in (dH, dS, dX, dW, dV):
                 d.free()
         return out
@@ -978,7 +1005,7 @@ class SpSolver(Solver):
         return out
 
 
-class SpGevSolver:
+class SpGevSolver(GevSolver):
     """GevSolver at itype 1 on fp32 data: the lowest nev pairs of H x = lambda S x for H32, S32 float32 / complex64 (Fortran order,
     S positive definite; the upper triangles are what is read).  Both are uploaded as they are and reduced in place on the device
     by the fp32 drivers (S = U^H U, C = U^{-H} H U^{-1}); an SpSolver then works on C where it lies (self.solver).  While this
@@ -986,91 +1013,34 @@ class SpGevSolver:
     GevSolver's; ritzv and residuals are fp64, the vectors fp32.  S not positive definite: ChaseHipError with .pivot."""
 
     def __init__(self, ctx, H32, S32, nev, nex):
-        assert H32.ndim == 2 and H32.shape[0] == H32.shape[1] and S32.shape == H32.shape
-        assert H32.dtype in (np.float32, np.complex64) and S32.dtype in (np.float32, np.complex64), \
-            "SpGevSolver takes fp32 matrices: round them yourself"
-        self.ctx = ctx
-        self.cplx = bool(H32.dtype == np.complex64 or S32.dtype == np.complex64)
-        self.N, self.nev, self.nex = H32.shape[0], nev, nex
-        self.H, self.S = H32, S32                          # the originals, for gev_residuals()
-        self.dC, self.dU = self._dev(H32), self._dev(S32)
-        self.solver = None
-        info = ctx.gev_reduce_sp(1, self.N, self.dC.ptr, self.N, self.dU.ptr, self.N, self.cplx)
-        if info > 0:
-            self.close()
-            raise GevSolver._pivot_error(info)
-        self.solver = SpSolver(ctx, None, nev, nex, h_on_device_ptr=self.dC.ptr, N=self.N, cplx=self.cplx, ldh=self.N)
+        assert self._is_fp32(H32) and self._is_fp32(S32), "SpGevSolver takes fp32 matrices: round them yourself"
+        super().__init__(ctx, H32, S32, nev, nex)
+
+    _solver_class = SpSolver
+
+    @staticmethod
+    def _is_fp32(A):
+        return A.dtype in (np.float32, np.complex64)
 
     def _dt(self):
         return np.complex64 if self.cplx else np.float32
 
-    def _dev(self, A):
-        return self.ctx.empty(A.shape, self._dt()).upload(A)
+    def _accepts(self, A):
+        return self._is_fp32(A) and super()._accepts(A)
 
-    close = GevSolver.close
-    set = GevSolver.set
-    get = GevSolver.get
-    solve = GevSolver.solve
-    stats = GevSolver.stats
-    resid = GevSolver.resid
-    ritzv = GevSolver.ritzv
-    reduced = GevSolver.reduced
-    factor = GevSolver.factor
-    start_vectors = GevSolver.start_vectors
+    def _reduce(self, factor, first=False):
+        return self.ctx.gev_reduce_sp(factor, self.N, self.dC.ptr, self.N, self.dU.ptr, self.N, self.cplx)
 
-    def update(self, H32, S32=None):
-        """GevSolver.update: the next pencil of a sequence, started from the previous vectors.  S32 = None: the overlap matrix
-        did not change, H is reduced with the stored factor (factor = 0, no Cholesky)."""
-        assert H32.shape == (self.N, self.N) and H32.dtype in (np.float32, np.complex64) and (H32.dtype == np.complex64) <= self.cplx
-        n, nc = self.N, self.nev + self.nex
-        if S32 is None:
-            self.dC.upload(H32)
-            self.ctx.gev_reduce_sp(0, n, self.dC.ptr, n, self.dU.ptr, n, self.cplx)
-        else:
-            assert S32.shape == H32.shape and S32.dtype in (np.float32, np.complex64) and (S32.dtype == np.complex64) <= self.cplx
-            dX = self._dev(self.solver.V)
-            try:
-                self.ctx.gev_backtransform_sp(n, nc, self.dU.ptr, n, dX.ptr, n, self.cplx)
-                self.dU.upload(S32)
-                self.dC.upload(H32)
-                info = self.ctx.gev_reduce_sp(1, n, self.dC.ptr, n, self.dU.ptr, n, self.cplx)
-                if info > 0:
-                    raise GevSolver._pivot_error(info)
-                self.ctx.gev_starttransform_sp(n, nc, self.dU.ptr, n, dX.ptr, n, self.cplx)
-                self.solver.V[...] = dX.download()
-            finally:
-                dX.free()
-            self.S = S32
-        self.H = H32
-        self.solver.set(approx=1)
+    def _backtransform(self, dX, ncols, plain=False):
+        self.ctx.gev_backtransform_sp(self.N, ncols, self.dU.ptr, self.N, dX.ptr, self.N, self.cplx)
 
-    def eigenpairs(self):
-        """(lambda[:nev] in fp64, X[:, :nev] in fp32): H X = S X diag(lambda), X^H S X = I"""
-        dX = self._dev(self.solver.V[:, :self.nev])
-        self.ctx.gev_backtransform_sp(self.N, self.nev, self.dU.ptr, self.N, dX.ptr, self.N, self.cplx)
-        X = dX.download()
-        dX.free()
-        return self.solver.ritzv[:self.nev].copy(), X
+    def _starttransform(self, dX, ncols):
+        self.ctx.gev_starttransform_sp(self.N, ncols, self.dU.ptr, self.N, dX.ptr, self.N, self.cplx)
 
-    def gev_residuals(self):
-        """|| H x_j - lambda_j S x_j ||_2, j < nev, in fp64 from the ORIGINAL fp32 matrices (uploaded again for this: two more
-        N^2 fp32 blocks while it runs): products with fp32 operands and an fp64 result, norms in fp64"""
-        lam, X = self.eigenpairs()
-        n, k = self.N, self.nev
-        full = lambda A: np.triu(A) + np.triu(A, 1).conj().T          # the triangle the reduction read
-        dH, dS, dX = self._dev(full(self.H)), self._dev(full(self.S)), self._dev(X)
-        dt64 = np.complex128 if self.cplx else np.float64
-        dW, dV = self.ctx.empty((n, k), dt64), self.ctx.empty((n, k), dt64)
-        out = np.zeros(k)
-        try:
-            self.ctx.gemm32w("N", n, k, n, 1.0, dH.ptr, n, dX.ptr, n, 0.0, dW.ptr, n, self.cplx)
-            self.ctx.gemm32w("N", n, k, n, 1.0, dS.ptr, n, dX.ptr, n, 0.0, dV.ptr, n, self.cplx)
-            check(lib.chase_hip_resid_norms(self.ctx.h, int(self.cplx), n, k, dW.ptr, n, dV.ptr, n, lam.ctypes.data,
-                                            out.ctypes.data, 0), "resid_norms")
-        finally:
-            for d in (dH, dS, dX, dW, dV):
-                d.free()
-        return out
+    def _residual_products(self, products):
+        """products with fp32 operands and an fp64 result"""
+        for dA, dB, dW in products:
+            self.ctx.gemm32w("N", self.N, dB.shape[1], self.N, 1.0, dA.ptr, self.N, dB.ptr, self.N, 0.0, dW.ptr, self.N, self.cplx)
 
 
 _sig("chase_hip_solver_create_pseudo", c_int, P(c_void_p), c_void_p, c_int, c_size_t, c_size_t, c_size_t, c_void_p,

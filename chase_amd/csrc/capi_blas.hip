@@ -14,22 +14,6 @@
 
 using namespace chase_hip;
 
-#define HIPCHK(x)                                                                                                      \
-    do {                                                                                                               \
-        hipError_t e_ = (x);                                                                                           \
-        if (e_ != hipSuccess) return hip_fail(e_, #x);                                                                 \
-    } while (0)
-#define KCHK(x, what)                                                                                                  \
-    do {                                                                                                               \
-        int e_ = (x);                                                                                                  \
-        if (e_) return hip_fail((hipError_t)e_, what);                                                                 \
-    } while (0)
-#define RCCHK(x)                                                                                                       \
-    do {                                                                                                               \
-        int r_ = (x);                                                                                                  \
-        if (r_) return r_;                                                                                             \
-    } while (0)
-
 namespace {
 constexpr int NB = 64;
 

@@ -28,7 +28,8 @@ struct chase_hip_ctx {
     size_t ws_bytes = 0;
     enum { BUF_TINV = 0, BUF_PANEL, BUF_SCAL, BUF_LAMBDA, BUF_RR, BUF_EIG, BUF_STEDC, BUF_APPLYQ, BUF_GEV_TINV, BUF_GEV_PANEL, BUF_GEV_DIAG, NBUF };
     // device scratch, grown on demand (BUF_EIG / BUF_STEDC: the projected eigensolver's blocks; BUF_GEV_*: capi_gev.hip, whose
-    // drivers call potrf_upper / trsm_right_upper and so cannot share BUF_TINV / BUF_PANEL with them)
+    // fp64 drivers call potrf_upper / trsm_right_upper and so cannot share BUF_TINV / BUF_PANEL with them; its fp32 drivers
+    // use the same three, sized in bytes)
     void* bufs[NBUF] = {};
     size_t buf_bytes[NBUF] = {};
     void* hstage = nullptr;      // pinned host staging (HEEVD round trip)
@@ -56,3 +57,20 @@ namespace chase_hip {
 int set_error(int code, const char* what);
 int hip_fail(hipError_t e, const char* where);
 }
+
+// the early returns of the C ABI's entry points: a HIP call, a kernel launcher's status, a nested entry point's return code
+#define HIPCHK(x)                                                                                                      \
+    do {                                                                                                               \
+        hipError_t e_ = (x);                                                                                           \
+        if (e_ != hipSuccess) return hip_fail(e_, #x);                                                                 \
+    } while (0)
+#define KCHK(x, what)                                                                                                  \
+    do {                                                                                                               \
+        int e_ = (x);                                                                                                  \
+        if (e_) return hip_fail((hipError_t)e_, what);                                                                 \
+    } while (0)
+#define RCCHK(x)                                                                                                       \
+    do {                                                                                                               \
+        int r_ = (x);                                                                                                  \
+        if (r_) return r_;                                                                                             \
+    } while (0)

@@ -23,7 +23,7 @@ __device__ __forceinline__ cd cmul_conj_a(cd a, cd b) { return cd{a.x * b.x + a.
 __device__ __forceinline__ cd cmul(cd a, cd b) { return cd{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 
 // Element i of a matrix stored as S = double (the fp64 entry points: the plain access) or S = float (the single-precision
-// generalized problem, capi_gev_sp.hip): widened on the way into LDS and rounded once on the way out, all arithmetic in fp64.
+// generalized problem, capi_gev.hip): widened on the way into LDS and rounded once on the way out, all arithmetic in fp64.
 template <bool CPLX, class S>
 __device__ __forceinline__ typename std::conditional<CPLX, cd, double>::type st_load(const S* p, long i)
 {

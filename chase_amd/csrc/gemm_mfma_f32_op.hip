@@ -1,5 +1,5 @@
 // gemm_mfma_f32_op.hip — C32 = alpha op(A32) B32 + beta C32 with op(A) = N or C: the product of the single-precision generalized
-// problem (capi_gev_sp.hip, chase_hip_gemm_s_op / _c_op).
+// problem (the _sp entry points of capi_gev.hip, chase_hip_gemm_s_op / _c_op).
 //
 // The kernel is gemm_f32_kernel of gemm_mfma_f32.hip, taken as text: that file instantiates its OPC operand path - A read
 // k-contiguous and transposed into the same m-contiguous LDS image the op N path builds, the conjugate a sign at the LDS store -

@@ -241,7 +241,7 @@ int narrow(bool cplx, char opA, int m, int n, int k, const float* alpha, const f
 }
 
 // narrow with op(A) = N or C (real: T as well), A for op = C a k x m array: launch(a, opc) starts the kernel.  The generalized
-// problem's single-precision drivers (capi_gev_sp.hip); narrow itself keeps refusing anything but N.
+// problem's single-precision drivers (capi_gev.hip); narrow itself keeps refusing anything but N.
 template <class Launch>
 int narrow_op(bool cplx, char opA, int m, int n, int k, const float* alpha, const float* A, long lda, const float* B, long ldb,
               const float* beta, float* C, long ldc, int bn, Launch&& launch)

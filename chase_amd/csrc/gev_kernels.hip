@@ -41,7 +41,7 @@ __device__ __forceinline__ double g_from_real(double r, double) { return r; }
 // c - a * b
 __device__ __forceinline__ gcd g_nfma(gcd a, gcd b, gcd c) { return gcd{c.x - (a.x * b.x - a.y * b.y), c.y - (a.x * b.y + a.y * b.x)}; }
 __device__ __forceinline__ double g_nfma(double a, double b, double c) { return c - a * b; }
-// Element i of a matrix stored as S = double (the plain access) or S = float (the single-precision drivers, capi_gev_sp.hip):
+// Element i of a matrix stored as S = double (the plain access) or S = float (the single-precision drivers of capi_gev.hip):
 // widened on the way into LDS, rounded once on the way out; the arithmetic of hegs2_diag is fp64 for both.
 template <class E, class S>
 __device__ __forceinline__ E g_load(const S* p, long i)

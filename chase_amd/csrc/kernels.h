@@ -36,7 +36,7 @@ constexpr int GEMM_F32_EOP = -77002;
 int gemm_f32(hipStream_t st, bool cplx, char opA, int m, int n, int k, const float* alpha, const float* A, long lda, const float* B,
              long ldb, const float* beta, float* C, long ldc, int num_cu, int tag = 0);
 // gemm_f32 with op(A) = N or C (real: T as well), A for op = C a k x m array: op N is gemm_f32 bit for bit, op C is op N on the
-// explicitly formed A^H bit for bit.  The product of the single-precision generalized problem (capi_gev_sp.hip).
+// explicitly formed A^H bit for bit.  The product of the single-precision generalized problem (capi_gev.hip).
 int gemm_f32_op(hipStream_t st, bool cplx, char opA, int m, int n, int k, const float* alpha, const float* A, long lda,
                 const float* B, long ldb, const float* beta, float* C, long ldc, int num_cu, int tag = 0);
 // the same product written and scaled in fp64: C64 = alpha op(A32) B32 + beta C64, op(A) = N or C (real: T as well), A for
@@ -152,7 +152,7 @@ int trmm_diag(hipStream_t st, bool cplx, bool op_c, const double* U, long ldu, d
 // A (n x n) <- A^H in place
 int conj_transpose_inplace(hipStream_t st, bool cplx, double* A, long lda, int n);
 
-// ---- the same cores on fp32 storage (capi_gev_sp.hip) ----
+// ---- the same cores on fp32 storage (the _sp entry points of capi_gev.hip) ----
 // potf2_trtri / trtri_diag / hegs2_diag: the kernels above instantiated for float matrices - loads widened, all arithmetic in
 // fp64 registers and LDS, one rounding on the way out (Tinv is fp32 too: it feeds the fp32 product).  The helpers address floats.
 int potf2_trtri(hipStream_t st, bool cplx, float* A, long lda, int nb, int joff, float* Tinv, int* info_dev);
@@ -165,5 +165,14 @@ int mirror_lower(hipStream_t st, float* A, long lda, int n, int ept, int zero_di
 int copy2d_sp(hipStream_t st, const float* src, long ld_src_f, float* dst, long ld_dst_f, long mf, int ncols);   // sp_kernels.hip
 // trmm_diag on fp32 data: v_mfma_f32_16x16x4_f32, fp32 accumulation
 int trmm_diag_sp(hipStream_t st, bool cplx, bool op_c, const float* U, long ldu, float* X, long ldx, int nb, int ncols);
+// the two under the names of their fp64 forms, for the drivers of capi_gev.hip that are written once for both precisions
+inline int copy2d(hipStream_t st, const float* src, long ld_src_f, float* dst, long ld_dst_f, long mf, int ncols)
+{
+    return copy2d_sp(st, src, ld_src_f, dst, ld_dst_f, mf, ncols);
+}
+inline int trmm_diag(hipStream_t st, bool cplx, bool op_c, const float* U, long ldu, float* X, long ldx, int nb, int ncols)
+{
+    return trmm_diag_sp(st, cplx, op_c, U, ldu, X, ldx, nb, ncols);
+}
 
 } // namespace chase_hip

@@ -186,7 +186,7 @@ def gev_residual_bound(H, S, U, C, lam, x, rho):
     return nU * rho + float(np.linalg.norm(wide(x))) * (t_h + t_s + t_x)
 
 
-# ---- numpy models of the device's blocked algorithms in fp32 (capi_gev_sp.hip) ---------------------------------------------------
+# ---- numpy models of the device's blocked algorithms in fp32 (capi_gev.hip, float) ---------------------------------------------------
 def model_trsm_left(R, Bp, n, op, **defects):
     """gev_refs.model_trsm_left on float32 data: numpy keeps the type, so every product and inverse is rounded to fp32"""
     assert np.asarray(R).dtype in (np.float32, np.complex64) and np.asarray(Bp).dtype in (np.float32, np.complex64)
